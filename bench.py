@@ -3,7 +3,12 @@
 table-walk hot path on the 10M x 256-char synthetic batch.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c3s|c5|c5w] [--also c3,c3s,c5,c5w|none]
-                    [--rows R] [--scaling strong|weak] [--graph off|scan]
+                    [--rows R] [--scaling strong|weak] [--graph off|scan] [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set-up, device pre-warm, W warm-up steps, the K timed steps, one JSON line.
+Everything else below (cold / steady steps, the gather check of N > 1, the further workloads, the extras, the CPU
+baseline, the ragged batches, C4's shard step) is measured with `--full`.  `--dump-outputs DIR` writes what the last
+timed step computed (see dump_outputs()).
 
 One "step" = one pass of the hot path over the whole device-resident batch: one kernel launch per GPU and, for
 N > 1, the gathers that bring the results to rank 0 (bitmap: one RCCL all-gather; find(): plus a fan-in of start /
@@ -260,6 +265,31 @@ class Ctx:
     pass
 
 
+DUMP_MAX_BYTES = 48 << 20   # above this the dump is a sample of rows (the whole dump stays under 64 MB)
+DUMP_SAMPLE_ROWS = 1 << 21
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, bitmap, start, end, n_rows):
+    """--dump-outputs: what the last timed step handed its caller, one value per row as float32 -- matched.npy (0 / 1: the
+    result bitmap) and for find() start.npy / end.npy (-1 where the row has no match).  When that is more than
+    DUMP_MAX_BYTES, the same fixed, seeded sample of rows is taken from each array and its row numbers go to row.npy
+    (float64).  The inputs are the seeded synthetic batch, so two builds given the same arguments can be compared file
+    for file."""
+    import numpy as np
+    from needle_amd.pattern import unpack_bitmap
+    arrays = {"matched": unpack_bitmap(bitmap, n_rows)}
+    if start is not None:
+        arrays["start"], arrays["end"] = start[:n_rows].cpu().numpy(), end[:n_rows].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    rows = None
+    if 4 * n_rows * len(arrays) > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, min(n_rows, DUMP_SAMPLE_ROWS), replace=False))
+        np.save(os.path.join(out_dir, "row.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), (a if rows is None else a[rows]).astype(np.float32))
+
+
 def verify_gather(sh, dev, row0, n_rows, total_rows, is_find, rank):
     """One extra step whose gathered results are checked against what every rank computed locally (see measure())."""
     import torch
@@ -314,6 +344,7 @@ def measure(workload, args, ctx, headline):
     from needle_amd.sharding import ShardedScan, shard_range
     from needle_amd.pattern import unpack_bitmap
     dev, world, rank, use_dist = ctx.dev, ctx.world, ctx.rank, ctx.use_dist
+    extras = args.full and not args.no_extras
     pattern, what, words = make_pattern(workload)
     if headline and args.regex is not None:  # not a BASELINE config: labelled as such in config.workload
         from needle_amd.pattern import DFACompiler
@@ -381,7 +412,7 @@ def measure(workload, args, ctx, headline):
     # The W warm-up steps and the K timed steps below are the contract's; this only makes them steady-state steps.
     # The same K steps COLD first (device idle for 0.3 s, no pre-warm): what a caller sees who scans one batch now and then.
     cold = None
-    if args.prewarm_ms > 0:
+    if args.full and args.prewarm_ms > 0:
         fence()
         time.sleep(0.3)
         tc = time.perf_counter()
@@ -423,10 +454,12 @@ def measure(workload, args, ctx, headline):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     kernel_ms = sum(a.elapsed_time(b) for a, b in events) / len(events)
+    if headline and args.dump_outputs and n_rows:
+        dump_outputs(args.dump_outputs, *sh.wait(last), n_rows)
     # K timed steps are a few ms: a longer run right behind them (>= 100 ms of steps, same protocol) says whether the K steps
     # were representative of the steady state.  `value` stays the contract's exactly-K-steps figure.
     steady = None
-    if n_rows or use_dist:
+    if args.full and (n_rows or use_dist):
         ks = max(args.steps, int(0.1 / max(elapsed / args.steps, 1e-6)) + 1)
         if use_dist:
             kt = torch.tensor([ks], dtype=torch.int64, device=dev)
@@ -448,7 +481,7 @@ def measure(workload, args, ctx, headline):
     # still print a clean line.  One more step, then: popcount of the gathered bitmap == sum over ranks of the shards'
     # popcounts, and for find() a position-weighted checksum of the gathered start / end == the sum of the ranks' own.
     gather_check = None
-    if use_dist:
+    if args.full and use_dist:
         gather_check = verify_gather(sh, dev, row0, n_rows, total_rows, is_find, rank)
 
     # algorithmic bytes: L*w input bytes + result bytes (1 bit/row; find adds 2 x int32/row)
@@ -531,7 +564,7 @@ def measure(workload, args, ctx, headline):
                 break
             except (OSError, KeyError, ValueError):
                 pass
-    if use_dist:
+    if args.full and use_dist:
         # scan and gather reported separately (each blocking, nothing overlapped) beside the step time
         # in which the gathers ARE overlapped with the next step's scan
         def blocking(fn, reps=10):
@@ -549,7 +582,7 @@ def measure(workload, args, ctx, headline):
                                        else ("ONE all-gather (RCCL) of the bitmap words: %d B per rank" % (sh.per_words * 8)),
                          "issued_by": "libneedle_hip.so (needle_multi_*)" if ctx.comm is not None else "torch.distributed",
                          "note": "gather_ms = blocking (scan + gathers) - blocking scan; inside the timed steps the gathers overlap the next scan"}
-    if use_dist and args.all_on_device is not None:
+    if args.full and use_dist and args.all_on_device is not None:
         # C4 rehearsal on ONE GPU (every rank's shard on the same device, gloo carrying the gathers): inside the timed steps the
         # ranks' kernels contend for the chip, so each rank also times its shard's scan ALONE, in turn -- what one GPU of an
         # 8-GPU node would spend on its 1/N of the batch.  N x the slowest of these against the N = 1 kernel time says what row
@@ -575,7 +608,7 @@ def measure(workload, args, ctx, headline):
                                  "what": "each rank's shard scanned alone on the shared device: 50 back-to-back launches between two HIP events; x_ranks = N x the "
                                          "slowest.  With N processes holding queues on one device this includes the driver's switching between "
                                          "their queues -- an upper bound on a rank's kernel, not the kernel (c4_shard_step has that)"}
-    if headline and rank == 0 and world == 1 and not args.no_extras:
+    if headline and rank == 0 and world == 1 and extras:
         out["roofline"]["device"] = {"name": props.name, "cus": props.multi_processor_count, "clock_mhz_nominal": ENGINE_CLOCK_MHZ}
         ceil = measured_read_ceiling(rows)
         if ceil:
@@ -584,7 +617,7 @@ def measure(workload, args, ctx, headline):
         mr, exact = must_read_bytes(workload if args.regex is None and args.op is None else "custom", pattern, rows, cw)
         out["must_read"] = {"bytes_per_step": mr, "GB/s": mr / step_s / 1e9, "exact": exact,
                             "note": "chars the reference loop touches before it stops x bytes/char (SURVEY.md s8d secondary denominator)"}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         # SURVEY.md s8d "results landed in host-visible memory": the same steps with the bitmap (and find()'s start /
         # end) copied to pinned host memory after every scan.  PCIe-bound for find (8 B per row); never the `value`.
         hb = torch.empty(sh.per_words, dtype=torch.int64).pin_memory()
@@ -658,7 +691,7 @@ def measure(workload, args, ctx, headline):
                                               "note": "needle_find_packed16_dev (the scan stores one dword per row itself) + D2H of 4 B per row; "
                                                       "scan_kernel_ms: that scan alone on the device"}
             del cw_, cr_, cc_, pk
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         # ... and PIPELINED ("results landed in host-visible memory" as a steady-state rate): two result sets; step k's D2H
         # runs on a copy stream under step k + 1's scan.  find(): the one-dword form the scan stores itself (4 B per row over PCIe).
         n_sets = 2
@@ -735,7 +768,7 @@ def measure(workload, args, ctx, headline):
                                                    "packed16 = one dword per row")
         if form == "packed8":
             out["host_landed"]["pipelined16"] = pipelined("packed16")  # round 5's figure: 4 result bytes per row over PCIe
-    if rank == 0 and world == 1 and not args.no_extras and workload in ("c2", "c3", "c3s", "c3x", "c5", "c3s16", "c3x16", "c3m16"):
+    if rank == 0 and world == 1 and extras and workload in ("c2", "c3", "c3s", "c3x", "c5", "c3s16", "c3x16", "c3m16"):
         # EVERY non-overlapping match of every row (the reference's repeated find()), one pass over
         # the batch (needle_find_all.hip; for dictionaries behind the n-gram candidate filter -- c3s -- that kernel's find-all form,
         # needle_ngram.hip): counts + dense per-row slots.  Its own figure, never the `value`.
@@ -797,7 +830,7 @@ def measure(workload, args, ctx, headline):
         torch.cuda.synchronize()
         out["find_all"]["count_pass_ms"] = (time.perf_counter() - t) / k2 * 1e3
         del fc, fs, fe
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(workload, pattern, rows, op_name, 10.0 if headline else 4.0)
     del rows, sh, graphs
     torch.cuda.empty_cache()
@@ -963,7 +996,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c3s", "c3x", "c5", "c5w", "c3s16", "c3x16", "c3m16", "c3u"], help="the headline workload")
     ap.add_argument("--also", default=None, help="comma list of further workloads measured into \"workloads\" "
-                    "(default: c3,c3s,c3x,c5,c5w,c3s16,c3x16 at 1 GPU, c3 at N > 1; 'none' for profiling runs; c3s16 / c3x16: the c3s / c3x dictionaries over UTF-16 rows)")
+                    "(default with --full: c3,c3s,c3x,c5,c5w,c3s16,c3x16,c3m16,c3u at 1 GPU, c3 at N > 1; without --full: none; 'none' for profiling runs; "
+                    "c3s16 / c3x16: the c3s / c3x dictionaries over UTF-16 rows)")
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows in total (strong) or per GPU (weak)")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"])
     ap.add_argument("--graph", default="off", choices=["off", "scan"], help="launch the scan as a HIP graph (experiment; plain launches are faster)")
@@ -980,7 +1014,15 @@ def main():
                     "the default keeps the line under the 8 KB the driver's log tail holds and sends the full JSON to stderr / bench_full.json")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the read-ceiling probe, the must-read byte count and the host-landed figure")
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline's K timed steps (off: the headline line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's results as DIR/<name>.npy (float32 per row; a seeded row sample above DUMP_MAX_BYTES, row numbers in row.npy as float64; --gpus 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        error_line(args, "--steps must be at least 1")
+        raise SystemExit(2)
+    if args.dump_outputs and args.gpus != 1:
+        error_line(args, "--dump-outputs needs --gpus 1")
+        raise SystemExit(2)
 
     import torch
     import torch.distributed as dist
@@ -1003,6 +1045,9 @@ def main():
     torch.cuda.set_device(local)
     ctx.dev = dev = torch.device("cuda", local)
     ctx.use_dist = use_dist = world > 1 or "RANK" in os.environ  # also under `torch.distributed.run --nproc-per-node 1`
+    if use_dist and args.dump_outputs:
+        error_line(args, "--dump-outputs needs a run without a launcher", rank == 0)
+        raise SystemExit(2)
     if use_dist and args.overlap == "on":
         # the scan kernel is one persistent workgroup per CU that owns the CU's whole LDS; leave a few CUs free so
         # that the RCCL kernels gathering the PREVIOUS step's results can run next to it instead of behind it
@@ -1031,7 +1076,7 @@ def main():
         if int(ok.item()) == 0:
             ctx.comm = None
     if args.also is None:
-        also = ["c3", "c3s", "c3x", "c5", "c5w", "c3s16", "c3x16", "c3m16", "c3u"] if world == 1 else ["c3"]
+        also = (["c3", "c3s", "c3x", "c5", "c5w", "c3s16", "c3x16", "c3m16", "c3u"] if world == 1 else ["c3"]) if args.full else []
         if args.regex or args.op or args.rows != 10_000_000:
             also = []
     else:
@@ -1055,7 +1100,7 @@ def main():
     }
     out.update(head)
     out["kernel_source_sha"] = kernel_source_sha()
-    if world == 1 and not use_dist and not args.no_extras and args.rows == 10_000_000 and args.regex is None and args.op is None:
+    if args.full and world == 1 and not use_dist and not args.no_extras and args.rows == 10_000_000 and args.regex is None and args.op is None:
         # C4's per-GPU share at 8 GPUs, measured on this one GPU: the step over a 1.25M-row shard of the
         # headline batch (and of C3's, whose find() gathers start / end) -- scan kernel vs whole step, i.e. what launch
         # overhead costs at that size.  No communication here; N > 1 runs report scan_ms / gather_ms themselves.
@@ -1081,14 +1126,16 @@ def main():
             except Exception as e:  # noqa: BLE001 -- a further workload must never cost the headline its line
                 r = {"error": "%s: %s" % (type(e).__name__, e)}
             out["workloads"][w] = r
-    if world == 1 and not use_dist and not args.no_extras and args.rows == 10_000_000 and args.regex is None and args.op is None and args.also is None:
+    if args.full and world == 1 and not use_dist and not args.no_extras and args.rows == 10_000_000 and args.regex is None and args.op is None and args.also is None:
         out["ragged"] = {}
         for w in ("c2r", "c3r"):
             try:
                 out["ragged"][w] = measure_ragged(w, args, ctx)
             except Exception as e:  # noqa: BLE001
                 out["ragged"][w] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(out), flush=True)  # a plain run: the headline's line is everything it measured
+    if rank == 0 and args.full:
         # The driver keeps the last 8 KB of stdout: the ONE line printed there is the contract's fields + roofline + cpu_baseline +
         # a compact digest of every workload (slim()); everything measured, with its notes, goes to stderr and bench_full.json.
         full = json.dumps(out)

@@ -11,6 +11,10 @@ SOURCES = ["needle_scan_find1.hip", "needle_scan_find2.hip", "needle_scan_contai
 HEADERS = ["needle_device.h", "needle_walk.h", "needle_scan.h", "needle_find_all.h", "needle_lower.h", "needle_regex.h", "needle_ngram.h", "needle_ngram_host.h", "needle_unicode_tables.h", os.path.join("..", "..", "include", "needle_hip.h")]
 
 
+TUNING_LIB = os.path.join(HERE, "libneedle_hip_tuning.so")
+TUNING_SOURCES = SOURCES + ["needle_dict.hip"]
+
+
 PROBE_LIB = os.path.join(HERE, "libneedle_probe.so")  # measurement aid for bench.py, not part of the product ABI
 PROBE_SRCS = [os.path.join(CSRC, "stream_probe.hip"), os.path.join(CSRC, "prefix_probe.hip"), os.path.join(CSRC, "ngram_probe.hip")]
 
@@ -24,11 +28,11 @@ def build_probe(force=False):
     return PROBE_LIB
 
 
-def _stale():
-    if not os.path.exists(LIB):
+def _stale(lib=LIB, sources=SOURCES):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    t = os.path.getmtime(lib)
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in sources + HEADERS)
 
 
 def _deps(path, seen=None):
@@ -53,12 +57,24 @@ def build(force=False, verbose=False):
     build_probe(force)
     if not force and not _stale():
         return LIB
+    return _build_lib(LIB, SOURCES, os.path.join(HERE, "build"), [], force, verbose)
+
+
+def build_tuning(force=False, verbose=False):
+    """The measurement build (what scripts/build_tuning.sh makes): the same sources with -DNEEDLE_TUNING -- switches that change
+    ANSWERS, never in libneedle_hip.so -- plus needle_dict.hip's two-sets-per-wave kernel, as libneedle_hip_tuning.so.  The
+    survivor-pool tests run that kernel through it (NEEDLE_LIB)."""
+    if not force and not _stale(TUNING_LIB, TUNING_SOURCES):
+        return TUNING_LIB
+    return _build_lib(TUNING_LIB, TUNING_SOURCES, os.path.join(HERE, "build", "tuning"), ["-DNEEDLE_TUNING"], force, verbose)
+
+
+def _build_lib(lib, sources, objdir, defines, force, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-x", "hip", "-Wall", "-Wno-unused-variable"]
-    objdir = os.path.join(HERE, "build")
+    flags = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-x", "hip", "-Wall", "-Wno-unused-variable"] + defines
     os.makedirs(objdir, exist_ok=True)
     procs, objs = [], []
-    for src in SOURCES:  # one hipcc per translation unit, all at once (the scan kernel's 96 instantiations dominate)
+    for src in sources:  # one hipcc per translation unit, all at once (the scan kernel's 96 instantiations dominate)
         obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(f) for f in _deps(os.path.join(CSRC, src))):
@@ -70,11 +86,11 @@ def build(force=False, verbose=False):
     for cmd, pr in procs:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
-    link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", LIB] + objs
+    link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", lib] + objs
     if verbose:
         print(" ".join(link))
     subprocess.check_call(link)
-    return LIB
+    return lib
 
 
 if __name__ == "__main__":

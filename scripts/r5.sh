@@ -3,7 +3,7 @@
 #   tests <pytest args>     pytest -m gpu on the given files / -k expression -> gpurun_out/r5/tests_<tag>.log
 #   fa [workload] [rows]    find-all probe: lock-step kernel vs the one-pass kernel, both result forms (A/B in one call)
 #   fa_prof                 rocprofv3 --kernel-trace --stats + PMC passes of the find-all kernels on C3 -> gpurun_out/r5/fa_prof/
-#   bench [args]            python bench.py [args] -> gpurun_out/r5/bench_<tag>.json
+#   bench [args]            python bench.py --full [args] -> bench_<tag>.json in the output folder
 #   py <script> [args]      python <script> [args] > gpurun_out/r5/<basename>.log
 #   pmc_py <tag> <script> [args]   PMC passes (VALU / SALU / LDS instructions, LDS conflicts, waits) of any script: per kernel, per launch
 cd /tmp && export TMPDIR=/tmp
@@ -47,7 +47,7 @@ PY
     head -5 $P/$w/t_kernel_stats.csv | cut -c1-160; head -5 $P/${w}_packed/t_kernel_stats.csv | cut -c1-160; cat $P/${w}_pmc.txt
   done ;;
 bench)
-  timeout 1700 python bench.py "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err; grep -v "^{" $O/bench_$TAG.err | tail -3; wc -c $O/bench_$TAG.json; tail -c 1200 $O/bench_$TAG.json ;;
+  timeout 1700 python bench.py --full "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err; grep -v "^{" $O/bench_$TAG.err | tail -3; wc -c $O/bench_$TAG.json; tail -c 1200 $O/bench_$TAG.json ;;
 profiles)
   # everything profiles/r05_* is made from (then: summarize_profile.py gpurun_out/prof_<w> 05 <w>, summarize_pmc.py 05)
   for w in c2 c3 c3s c3x c5 c5w c3x16; do scripts/profile.sh $w > gpurun_out/profile_$w.log 2>&1; done
@@ -64,13 +64,13 @@ profiles)
   rm -rf $O/fa_prof; $0 fa_prof c3 > $O/fa_prof.log 2>&1
   NEEDLE_FIND_ALL_LOCKSTEP=0 R5_SUB=ls0 bash -c 'P=gpurun_out/r5/fa_prof_ls0; mkdir -p $P; FIND_ALL_PROBE_PACKED=1 FIND_ALL_PROBE_DENSE_ONLY=1 rocprofv3 --kernel-trace --stats --output-format csv -d $P/c3_packed -o t -- python scripts/find_all_probe.py c3 10000000 32 > $P/c3_packed.json 2> $P/err.log; find $P -name "*_kernel_trace.csv" -delete; find $P -name "*_agent_info.csv" -delete'
   for w in c3 c3s c3x c2 c5; do python scripts/find_all_probe.py $w 10000000 32 check 2>/dev/null | tail -1 > $O/fa_$w.json; FIND_ALL_PROBE_PACKED=1 python scripts/find_all_probe.py $w 10000000 32 2>/dev/null | tail -1 > $O/fa_${w}_packed.json; done
-  timeout 1700 python bench.py > $O/bench_default.json 2> $O/bench_default.err; python scripts/bench_digest.py $O/bench_default.json ;;
+  timeout 1700 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; python scripts/bench_digest.py $O/bench_default.json ;;
 repeat)
   # repeat <workload> <n> [bench args]: the same bench line n times in one lease (timed / cold / steady ms, kernel ms), clocks before and after
   w=$1; n=$2; shift 2
   rocm-smi --showclocks 2>/dev/null | grep -E "sclk|mclk|fclk" | head -6
   for i in $(seq $n); do
-    python bench.py --workload $w --also none --no-cpu-baseline --no-extras --full-line "$@" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$w', 'timed', round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'cold', round(d['cold']['ms_per_step'],4), 'steady', round(d['steady']['ms_per_step'],4), 'frac', round(d['roofline']['frac'],4))"
+    python bench.py --full --workload $w --also none --no-cpu-baseline --no-extras --full-line "$@" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$w', 'timed', round(d['ms_per_step'],4), 'kernel', round(d['roofline']['kernel_ms'],4), 'cold', round(d['cold']['ms_per_step'],4), 'steady', round(d['steady']['ms_per_step'],4), 'frac', round(d['roofline']['frac'],4))"
   done
   rocm-smi --showclocks 2>/dev/null | grep -E "sclk|mclk|fclk" | head -6 ;;
 pmc_py)

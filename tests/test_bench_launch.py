@@ -1,6 +1,6 @@
 """bench.py's start-up contract: `python bench.py --gpus N` must start as the driver calls it -- no launcher, no
 RANK / WORLD_SIZE -- and a run that cannot start prints ONE JSON line carrying "error", never a traceback.  (The run itself is
-rehearsed on a GPU in tests/test_gpu_multi_device.py::test_c4_rehearsal_eight_ranks_full_batch_on_one_gpu.)"""
+rehearsed on a GPU in tests/test_gpu_multi_device.py::test_c4_rehearsal_three_ranks_full_batch_on_one_gpu.)"""
 import json
 import os
 import subprocess
@@ -82,3 +82,55 @@ def test_stdout_digest_stays_under_8_kb():
         assert k in line, k
     assert set(line["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"} and line["cpu_baseline"]["kind"] in ("port", "reference")
     assert set(full["workloads"]) == set(line["workloads"]) and "ragged" in line and line["config"]["workload"].startswith("c2")
+
+
+def _bits_words(n, seed):
+    import numpy as np
+    import torch
+    bits = np.random.default_rng(seed).random(n) < 0.4
+    pad = np.zeros((-n) % 64, dtype=bool)
+    return bits, torch.from_numpy(np.packbits(np.concatenate([bits, pad]), bitorder="little").view(np.int64).copy())
+
+
+def test_dump_outputs_writes_every_row_within_the_budget(tmp_path):
+    """--dump-outputs, containedIn: the result bitmap as one float32 0 / 1 per row, every row, no row numbers."""
+    import numpy as np
+    import bench
+    n = 1000
+    bits, words = _bits_words(n, 1)
+    bench.dump_outputs(str(tmp_path / "d"), words, None, None, n)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["matched.npy"]
+    m = np.load(tmp_path / "d" / "matched.npy")
+    assert m.dtype == np.float32 and m.shape == (n,) and (m == bits).all()
+
+
+def test_dump_outputs_samples_rows_above_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs, find(): matched / start / end as float32; above DUMP_MAX_BYTES the same seeded sample of rows from each
+    array, its row numbers (sorted, distinct) in row.npy as float64 -- and the same sample on every run."""
+    import numpy as np
+    import torch
+    import bench
+    n = 5000
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 3 * n - 1)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ROWS", 700)
+    bits, words = _bits_words(n, 2)
+    start = torch.from_numpy(np.where(bits, np.arange(n) % 200, -1).astype(np.int32))
+    end = torch.where(start >= 0, start + 5, start)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), words, start, end, n)
+    f = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("row", "matched", "start", "end")}
+    assert f["row"].dtype == np.float64 and all(f[k].dtype == np.float32 for k in ("matched", "start", "end"))
+    rows = f["row"].astype(np.int64)
+    assert rows.shape == (700,) and (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n
+    assert (f["matched"] == bits[rows]).all() and (f["start"] == start.numpy()[rows]).all() and (f["end"] == end.numpy()[rows]).all()
+    for k in f:
+        assert (np.load(tmp_path / "b" / (k + ".npy")) == f[k]).all()
+
+
+def test_bench_argument_guards_are_json_error_lines(tmp_path):
+    """--steps below 1, and --dump-outputs on more than one GPU, stop before any work with ONE error line (exit 2)."""
+    for args, msg in ((["--steps", "0"], "--steps must be at least 1"), (["--gpus", "2", "--dump-outputs", str(tmp_path / "d")], "--dump-outputs needs --gpus 1")):
+        proc = subprocess.run([sys.executable, "bench.py"] + args, capture_output=True, text=True, cwd=ROOT, env=CLEAN, timeout=300)
+        d = _one_line(proc)
+        assert proc.returncode == 2 and d["value"] is None and d["error"] == msg
+    assert not (tmp_path / "d").exists()

@@ -86,7 +86,7 @@ def test_one_very_long_row():
 
 
 @pytest.mark.gpu
-def test_stripe_path_equals_lane_path_on_ordinary_batches(monkeypatch):
+def test_stripe_path_equals_lane_path_on_ordinary_batches(monkeypatch, tmp_path):
     """The two work splits are interchangeable: forcing the stripe path on a short-row batch (NEEDLE_LONG_ROWS is read
     once per process, so the forced run happens in a subprocess) gives the same bits as the default path."""
     import os
@@ -108,7 +108,7 @@ np.save(sys.argv[1], np.concatenate([c, m, unpack_bitmap(fw, 3000), fs.cpu().num
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = []
     for force in ("0", "1"):
-        path = "/tmp/needle_long_rows_%s.npy" % force
+        path = str(tmp_path / ("needle_long_rows_%s.npy" % force))
         env = dict(os.environ, NEEDLE_LONG_ROWS=force)
         subprocess.check_call([sys.executable, "-c", code, path], cwd=root, env=env)
         out.append(np.load(path))

@@ -157,7 +157,7 @@ def test_bench_two_ranks_on_one_gpu(workload):
     import subprocess
     import sys
     from conftest import ROOT
-    base = [sys.executable, "bench.py", "--workload", workload, "--rows", "200000", "--steps", "3", "--warmup", "1", "--also", "none",
+    base = [sys.executable, "bench.py", "--full", "--workload", workload, "--rows", "200000", "--steps", "3", "--warmup", "1", "--also", "none",
             "--no-cpu-baseline", "--no-extras", "--full-line"]
     one = subprocess.run(base, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -181,57 +181,64 @@ def test_bench_two_ranks_on_one_gpu(workload):
 
 
 @pytest.mark.gpu
-def test_c4_rehearsal_eight_ranks_full_batch_on_one_gpu():
-    """C4 without an 8-GPU node: `bench.py --gpus 8` end to end on ONE GPU on the real 10^7-row batch -- eight
-    processes, shards of 1 250 048 rows on 64-row boundaries, gloo carrying the gathers, gather_verified, scan_ms / gather_ms --
-    and what row sharding itself costs: 8 x the slowest rank's shard kernel (timed alone on the device) within 15 % of the N = 1
-    kernel.  Rows are independent units (DFAClassBuilder.java:669-699: a Matcher per haystack), so nothing else can differ."""
+def test_c4_rehearsal_three_ranks_full_batch_on_one_gpu():
+    """C4 without a multi-GPU node: `bench.py --gpus 3` end to end on ONE GPU on the real 10^7-row batch -- three
+    processes (with this test's own process and the launcher, five hold the device at once), shards of 3 333 376 rows on 64-row
+    boundaries and a shorter last one, gloo carrying the gathers, gather_verified, scan_ms / gather_ms -- and what row sharding
+    itself costs: N x the slowest shard's kernel (timed alone on the device) within 15 % of the N = 1 kernel, for N = 3 and for
+    the 1 250 048-row shard of an 8-GPU node.  Rows are independent units (DFAClassBuilder.java:669-699: a Matcher per haystack),
+    so nothing else can differ."""
     import json
     import os
     import subprocess
     import sys
     from conftest import ROOT
     for workload in ("c2", "c3"):
-        base = [sys.executable, "bench.py", "--workload", workload, "--steps", "10", "--warmup", "2", "--also", "none", "--no-cpu-baseline", "--no-extras", "--full-line"]
+        base = [sys.executable, "bench.py", "--full", "--workload", workload, "--steps", "10", "--warmup", "2", "--also", "none", "--no-cpu-baseline",
+                "--no-extras", "--full-line"]
         one = subprocess.run(base, capture_output=True, text=True, cwd=ROOT, timeout=900)
         assert one.returncode == 0, one.stderr[-2000:]
         d1 = json.loads(one.stdout.strip().splitlines()[-1])
-        # the command form the driver uses at N = 1, with --gpus 8: NO launcher and no RANK / WORLD_SIZE in the environment --
-        # bench.py starts its eight ranks itself (bench.self_launch) and rank 0's line is the only line on stdout
-        cmd = [sys.executable, "bench.py", "--gpus", "8", "--backend", "gloo", "--all-on-device", "0"] + base[2:]
+        # the command form the driver uses at N = 1, with --gpus 3: NO launcher and no RANK / WORLD_SIZE in the environment --
+        # bench.py starts its three ranks itself (bench.self_launch) and rank 0's line is the only line on stdout
+        cmd = [sys.executable, "bench.py", "--gpus", "3", "--backend", "gloo", "--all-on-device", "0"] + base[2:]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-        eight = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=1800, env=env)
-        assert eight.returncode == 0, eight.stderr[-3000:]
-        lines = [ln for ln in eight.stdout.strip().splitlines() if ln.startswith("{")]
+        three = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=1800, env=env)
+        assert three.returncode == 0, three.stderr[-3000:]
+        lines = [ln for ln in three.stdout.strip().splitlines() if ln.startswith("{")]
         assert len(lines) == 1
-        d8 = json.loads(lines[0])
-        assert d8["n_gpus"] == 8 and d8["scaling"] == "strong" and d8["config"]["rows_total"] == 10_000_000 and d8["config"]["rows_per_gpu"] == 1_250_048
-        assert d8["gather_verified"] is True and d8["gather_check"]["popcount_gathered"] == d8["gather_check"]["popcount_ranks"]
+        d3 = json.loads(lines[0])
+        assert d3["n_gpus"] == 3 and d3["scaling"] == "strong" and d3["config"]["rows_total"] == 10_000_000 and d3["config"]["rows_per_gpu"] == 3_333_376
+        assert d3["gather_verified"] is True and d3["gather_check"]["popcount_gathered"] == d3["gather_check"]["popcount_ranks"]
         if workload == "c3":
-            assert d8["gather_check"]["checksum_gathered"] == d8["gather_check"]["checksum_ranks"]
-            assert "one dword per row" in d8["config"]["result"]
-        assert abs(d8["matched_fraction"] - d1["matched_fraction"]) < 1e-12
-        assert d8["scan_ms"] > 0 and "gather_ms" in d8 and d8["value"] > 0
+            assert d3["gather_check"]["checksum_gathered"] == d3["gather_check"]["checksum_ranks"]
+            assert "one dword per row" in d3["config"]["result"]
+        assert abs(d3["matched_fraction"] - d1["matched_fraction"]) < 1e-12
+        assert d3["scan_ms"] > 0 and "gather_ms" in d3 and d3["value"] > 0
         if workload == "c2":
             # N = 1 through the same entry point stays the plain run (no launcher, no process group): within 3 % of it
             again = subprocess.run(base + ["--gpus", "1"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
             assert again.returncode == 0, again.stderr[-2000:]
             da = json.loads(again.stdout.strip().splitlines()[-1])
             assert da["n_gpus"] == 1 and abs(da["roofline"]["kernel_ms"] / d1["roofline"]["kernel_ms"] - 1.0) < 0.03, (da["roofline"], d1["roofline"])
-        # what sharding itself costs: one GPU's shard (1 250 048 rows) scanned by ONE process on the same device, x 8, against the
-        # N = 1 kernel.  (The ranks' own solo timings inside the 8-process run are reported too, but with eight processes holding
-        # queues on one device they include the driver's switching between them: an upper bound only.)
-        shard = subprocess.run(base + ["--rows", "1250048"], capture_output=True, text=True, cwd=ROOT, timeout=900)
-        assert shard.returncode == 0, shard.stderr[-2000:]
-        ds = json.loads(shard.stdout.strip().splitlines()[-1])
-        k1, k8 = d1["roofline"]["kernel_ms"], 8 * ds["roofline"]["kernel_ms"]
-        # measured (profiles/r04_c4_rehearsal.md): c2 +13 % (0.405 -> 8 x 0.0572 ms), c3 +28 % (0.404 -> 8 x 0.0647 ms: a 65 us launch of
-        # the big-table find kernel pays the program's staging into LDS and 4.8 groups per wave -- 5 on some, 4 on others -- in full)
-        # (boxes differ: c2 came out at +13 % and +17 % on two of them; the bounds leave that room)
-        assert abs(k8 / k1 - 1.0) < (0.25 if workload == "c2" else 0.40), (workload, k1, k8)
-        assert d8["solo_kernel_ms"]["max_over_ranks"] >= 0.8 * ds["roofline"]["kernel_ms"], (d8["solo_kernel_ms"], ds["roofline"]["kernel_ms"])
-        print("C4 rehearsal %s: N=1 kernel %.4f ms, 8 x shard kernel %.4f ms, 8-process solo x8 %.4f ms, step %.4f ms (scan %.4f + gather %.4f)" % (
-            workload, k1, k8, d8["solo_kernel_ms"]["x_ranks"], d8["ms_per_step"], d8["scan_ms"], d8["gather_ms"]))
+        # what sharding itself costs: one GPU's shard scanned by ONE process on the same device, x N, against the N = 1 kernel.  (The
+        # ranks' own solo timings inside the 3-process run are reported too, but with several processes holding queues on one device
+        # they include the driver's switching between them: an upper bound only.)
+        k1 = d1["roofline"]["kernel_ms"]
+        for n_gpus, shard_rows in ((3, 3_333_376), (8, 1_250_048)):
+            shard = subprocess.run(base + ["--rows", str(shard_rows)], capture_output=True, text=True, cwd=ROOT, timeout=900)
+            assert shard.returncode == 0, shard.stderr[-2000:]
+            ds = json.loads(shard.stdout.strip().splitlines()[-1])
+            kn = n_gpus * ds["roofline"]["kernel_ms"]
+            # measured at N = 8 (profiles/r04_c4_rehearsal.md): c2 +13 % (0.405 -> 8 x 0.0572 ms), c3 +28 % (0.404 -> 8 x 0.0647 ms: a 65 us
+            # launch of the big-table find kernel pays the program's staging into LDS and 4.8 groups per wave -- 5 on some, 4 on others -- in
+            # full) (boxes differ: c2 came out at +13 % and +17 % on two of them; the bounds leave that room)
+            assert abs(kn / k1 - 1.0) < (0.25 if workload == "c2" else 0.40), (workload, n_gpus, k1, kn)
+            if n_gpus == 3:
+                assert d3["solo_kernel_ms"]["max_over_ranks"] >= 0.8 * ds["roofline"]["kernel_ms"], (d3["solo_kernel_ms"], ds["roofline"]["kernel_ms"])
+            print("C4 rehearsal %s: N=1 kernel %.4f ms, %d x shard kernel %.4f ms" % (workload, k1, n_gpus, kn))
+        print("C4 rehearsal %s: 3-process solo x3 %.4f ms, step %.4f ms (scan %.4f + gather %.4f)" % (
+            workload, d3["solo_kernel_ms"]["x_ranks"], d3["ms_per_step"], d3["scan_ms"], d3["gather_ms"]))
 
 
 PACKED = r'''

@@ -113,7 +113,7 @@ def test_skewed_lengths_run_as_length_classes():
 
 
 @pytest.mark.gpu
-def test_large_host_batches_are_chunked():
+def test_large_host_batches_are_chunked(tmp_path):
     """Host batches larger than the device-resident chunk size run chunk by chunk (64-row aligned); the chunk size is read
     once per process, so the small-chunk run happens in a subprocess."""
     import os
@@ -140,7 +140,7 @@ np.save(sys.argv[1], np.concatenate([c.view(np.int64), m.view(np.int64), fw.view
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = []
     for chunk in ("0", str(1 << 20)):  # 0: library default (one chunk), 1 MiB: 8 chunks of 4096 rows
-        path = "/tmp/needle_chunk_%s.npy" % chunk
+        path = str(tmp_path / ("needle_chunk_%s.npy" % chunk))
         env = dict(os.environ)
         if chunk != "0":
             env["NEEDLE_HOST_CHUNK_BYTES"] = chunk

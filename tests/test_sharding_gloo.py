@@ -1,4 +1,4 @@
-"""N > 1 path on CPU: world_size-2 (and 3) gloo process groups exercising needle_amd/sharding.py -- contiguous
+"""N > 1 path on CPU: world_size-2 (and 3, and 8: the C4 node) gloo process groups exercising needle_amd/sharding.py -- contiguous
 row blocks on 64-row boundaries, the bitmap / per-row gathers to rank 0 -- against the unsharded CPU oracle.
 (The per-shard verdicts come from the oracle here; on the GPU box the same code path carries kernel output.)"""
 import os
@@ -129,7 +129,7 @@ def _worker(rank, world, port, total_rows, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,total_rows", [(2, 1000), (3, 64 * 7 + 5), (2, 1)])
+@pytest.mark.parametrize("world,total_rows", [(2, 1000), (3, 64 * 7 + 5), (2, 1), (8, 64 * 8 * 3 + 17)])
 def test_row_sharding_and_gather(world, total_rows, oracle_lib):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -165,3 +165,4 @@ def test_shard_ranges_partition_the_batch():
                 assert row0 % 64 == 0 or n == 0
                 nxt = row0 + n
             assert nxt == total
+    assert [shard_range(10_000_000, 8, r)[1] for r in range(8)] == [1_250_048] * 7 + [10_000_000 - 7 * 1_250_048]  # C4's shards
