@@ -15,7 +15,7 @@ EXPORTS = [
     "needle_pack_start_end16_dev", "needle_unpack_start_end16_dev", "needle_matches_host",
     "needle_contained_in_host", "needle_find_host", "needle_find_compact_dev", "needle_find_compact_host", "needle_find_packed16_host", "needle_find_packed8_host", "needle_matcher_create", "needle_matcher_destroy",
     "needle_matcher_matches", "needle_matcher_contained_in", "needle_matcher_find", "needle_matcher_find_range",
-    "needle_matcher_start", "needle_matcher_end", "needle_rows_from_packed_dev", "needle_matches_packed_host",
+    "needle_matcher_start", "needle_matcher_end", "needle_rows_from_packed_dev", "needle_matches_packed_dev", "needle_contained_in_packed_dev", "needle_find_packed_dev", "needle_matches_packed_host",
     "needle_contained_in_packed_host", "needle_find_packed_host",
     "needle_multi_create", "needle_multi_destroy", "needle_multi_device_count", "needle_multi_stream", "needle_multi_transport", "needle_multi_scan",
     "needle_multi_sync", "needle_scan_host_multi", "needle_multi_unique_id", "needle_multi_create_rank",
@@ -134,6 +134,9 @@ def lib():
     L.needle_find_packed16_host.argtypes = [VP, P(BatchView), VP, VP]
     L.needle_find_packed8_host.argtypes = [VP, P(BatchView), VP, VP]
     L.needle_rows_from_packed_dev.argtypes = [P(PackedView), VP, ctypes.c_uint64, VP, VP, VP]
+    for n in ("needle_matches_packed_dev", "needle_contained_in_packed_dev"):
+        getattr(L, n).argtypes = [VP, P(PackedView), VP, VP]
+    L.needle_find_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP]
     for n in ("needle_matches_packed_host", "needle_contained_in_packed_host"):
         getattr(L, n).argtypes = [VP, P(PackedView), VP]
     L.needle_find_packed_host.argtypes = [VP, P(PackedView), VP, VP, VP]

@@ -19,6 +19,7 @@
 
 namespace needle {
 hipError_t launch_scan(int op, int char_width, const ScanArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_packed(int op, int char_width, const PackedArgs &a, int n_cus, hipStream_t stream); // needle_packed_find2.hip
 bool shape_for_program(const ProgHeader &h, int char_width, int *waves, int *chb, int *tiles_in_f_rows);
 hipError_t launch_find_all(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream); // needle_find_all.hip
 hipError_t launch_find_all_lockstep(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream); // needle_find_all_ls.hip
@@ -1292,8 +1293,72 @@ static int run_packed_host_one(const needle_pattern *p, int op, const needle_pac
 #undef HIP_TRY_C
 }
 
+// Packed device batches scanned as they lie (needle_packed.h): no conversion to fixed-stride rows, no host synchronisation.  The
+// program is chosen as run_dev's scan-kernel path chooses it -- the lengths form where find_lengths_for() allows it, else the
+// backward program -- so that one lowering serves both layouts and the answers are the same.
+static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_view *v, uint64_t *d_bitmap, int32_t *d_start,
+                          int32_t *d_end, void *stream) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    if (!d_bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
+    if (op == OP_FIND && (!d_start || !d_end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    const int which = op == OP_MATCHES ? W_MATCHES : op == OP_CONTAINED_IN ? W_CONTAINED_IN : W_FORWARDS;
+    const int cw = (int)v->char_width;
+    const bool need_backward = op == OP_FIND && p->t.fixed_len < 0;
+    const DevProgram *fp = nullptr;
+    int n_cus = 0;
+    rc = get_program(p, which, cw, need_backward ? 2 : 0, &fp, &n_cus);
+    if (rc) return rc;
+    bool lengths_form = false;
+    if (need_backward && find_lengths_for(fp->prog.hdr.mode)) {
+        const DevProgram *lp = nullptr;
+        rc = get_program(p, W_FORWARDS, cw, 7, &lp, nullptr);
+        if (rc) return rc;
+        static const bool force_tables = getenv("NEEDLE_FIND_LENGTHS") && atoi(getenv("NEEDLE_FIND_LENGTHS")) > 1; // (as run_dev)
+        if (lp && fp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR && !force_tables) lp = nullptr;
+        if (lp) fp = lp, lengths_form = true;
+    }
+    PackedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s.rows = (const uint8_t *)v->data;
+    a.s.n_rows = v->n_rows;
+    a.s.prog = fp->d_blob;
+    a.s.hdr = fp->prog.hdr;
+    a.s.fixed_len = -1;
+    if (op == OP_FIND) {
+        a.s.fixed_len = p->t.fixed_len;
+        if (a.s.fixed_len < 0 && !lengths_form) {
+            const DevProgram *bp = nullptr;
+            rc = get_program(p, W_BACKWARDS, cw, 1, &bp, nullptr);
+            if (rc) return rc;
+            a.s.bprog = bp->d_blob;
+            a.s.bhdr = bp->prog.hdr;
+        }
+    }
+    a.s.bitmap = d_bitmap;
+    a.s.start = d_start;
+    a.s.end = d_end;
+    a.offsets = v->offsets;
+    HIP_TRY(launch_packed(op, cw, a, n_cus, (hipStream_t)stream));
+    return NEEDLE_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 extern "C" {
+
+int needle_matches_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, void *s) {
+    return run_packed_dev(p, OP_MATCHES, v, bm, nullptr, nullptr, s);
+}
+int needle_contained_in_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, void *s) {
+    return run_packed_dev(p, OP_CONTAINED_IN, v, bm, nullptr, nullptr, s);
+}
+int needle_find_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, int32_t *st, int32_t *en, void *s) {
+    return run_packed_dev(p, OP_FIND, v, bm, st, en, s);
+}
 
 int needle_rows_from_packed_dev(const needle_packed_view *v, void *d_rows, uint64_t row_stride, uint32_t *d_lengths,
                                 int32_t *d_overflow, void *stream) {

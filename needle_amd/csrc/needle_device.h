@@ -144,6 +144,14 @@ struct ScanArgs {
                              // a 128-byte line hands them to its wave's pool and ends; 0 = off
 };
 
+// The packed-rows scan kernel (needle_packed.h): rows are code units [offsets[r], offsets[r + 1]) of `s.rows`.
+struct PackedArgs {
+    ScanArgs s;               // FIRST member: the backward walk reads the program headers at ScanArgs offsets of the kernarg
+                              // segment.  Used: rows (the view's data), n_rows, prog / hdr, bprog / bhdr, fixed_len,
+                              // tiles_in_f_rows, bitmap, start, end.
+    const uint64_t *offsets;  // n_rows + 1 entries (device)
+};
+
 // Long rows of table-mode automata (needle_stripe.hip, "speculative stripes"): every stripe is first scanned as a row of
 // its own from the START state (the tiled kernel, all stripes in parallel); then each stripe whose true entry state
 // differs is re-walked next to the speculative run until the two states meet.

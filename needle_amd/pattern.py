@@ -732,8 +732,10 @@ class Pattern:
         return words, se
 
     # ---- haystacks packed back to back (one char buffer + offsets: what a JNI host gets from a String[])
-    def _run_packed_host(self, op, data, offsets):
+    def _run_packed_host(self, op, data, offsets, stream=None, out=None):
         L = _lib.lib()
+        if not isinstance(data, np.ndarray) and type(data).__module__.startswith("torch") and data.is_cuda:
+            return self._run_packed_dev(op, data, offsets, stream, out)
         data = np.ascontiguousarray(data)
         if data.dtype == np.int16:
             data = data.view(np.uint16)
@@ -752,14 +754,50 @@ class Pattern:
         _check(fn(self._h, ctypes.byref(v), words.ctypes.data))
         return words
 
-    def matches_packed(self, data, offsets):
-        return self._run_packed_host("matches", data, offsets)
+    def _run_packed_dev(self, op, data, offsets, stream, out):
+        """Device tensors: needle_*_packed_dev -- the packed rows scanned as they lie, results as device tensors."""
+        import torch
+        L = _lib.lib()
+        assert data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), \
+            "data: 1-D uint8 or (u)int16 code units"
+        assert isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.device == data.device, "offsets: on data's device"
+        assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1, \
+            "offsets: 1-D int64, n + 1 entries"
+        n = offsets.numel() - 1
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        with torch.cuda.device(data.device):
+            s = torch.cuda.current_stream(data.device).cuda_stream if stream is None else stream
+            if out is not None:  # caller-owned result buffers (at least as large as the results)
+                words = out[0] if isinstance(out, (tuple, list)) else out
+                assert words.is_cuda and words.dtype == torch.int64 and words.numel() >= (n + 63) // 64
+            else:
+                words = torch.empty((n + 63) // 64, dtype=torch.int64, device=data.device)
+            if op == "find":
+                if out is not None:
+                    st, en = out[1], out[2]
+                    assert st.dtype == torch.int32 and en.dtype == torch.int32 and st.numel() >= n and en.numel() >= n
+                else:
+                    st = torch.empty(n, dtype=torch.int32, device=data.device)
+                    en = torch.empty(n, dtype=torch.int32, device=data.device)
+                _check(L.needle_find_packed_dev(self._h, ctypes.byref(v), words.data_ptr(), st.data_ptr(), en.data_ptr(), s))
+                return words, st, en
+            fn = L.needle_matches_packed_dev if op == "matches" else L.needle_contained_in_packed_dev
+            _check(fn(self._h, ctypes.byref(v), words.data_ptr(), s))
+            return words
 
-    def contained_in_packed(self, data, offsets):
-        return self._run_packed_host("contained_in", data, offsets)
+    def matches_packed(self, data, offsets, stream=None, out=None):
+        """matches() of every packed row: numpy data + offsets -> host path (upload, run, download); device tensors (1-D uint8 |
+        (u)int16 data, int64 offsets[n + 1]) -> needle_matches_packed_dev, bitmap words as a device tensor.  stream / out: as
+        matches_batch (device tensors only)."""
+        return self._run_packed_host("matches", data, offsets, stream, out)
 
-    def find_packed(self, data, offsets):
-        return self._run_packed_host("find", data, offsets)
+    def contained_in_packed(self, data, offsets, stream=None, out=None):
+        return self._run_packed_host("contained_in", data, offsets, stream, out)
+
+    def find_packed(self, data, offsets, stream=None, out=None):
+        """(bitmap words, start, end) of every packed row; device tensors give device tensors (needle_find_packed_dev)."""
+        return self._run_packed_host("find", data, offsets, stream, out)
 
     def find_strings(self, strings):
         """find() over a list of str (UTF-16 code units, like java.lang.String) -> (matched bool[n], start, end)."""

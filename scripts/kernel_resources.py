@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""VGPRs / scratch of every instantiation of the tiled scan kernel (cross-compiled here, no GPU needed): the kernels run
-16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  python scripts/kernel_resources.py [--all]"""
+"""VGPRs / scratch of every instantiation of the tiled scan kernel and of the packed-rows scan kernel (cross-compiled here, no
+GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
+LDS is the program plus one window (the tile) per wave, sized at launch: listed as the window per wave.
+python scripts/kernel_resources.py [--all]"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "needle_amd", "csrc")
@@ -8,7 +10,8 @@ names = {"0": "matches", "1": "containedIn", "2": "find"}
 modes = {"0": "pack", "1": "table8", "2": "table16", "3": "hbm", "4": "pair", "5": "hot-rows", "6": "sparse"}
 procs = []
 tmp = tempfile.mkdtemp()
-for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", "needle_scan_find2"):
+for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", "needle_scan_find2",
+           "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
                                          "-S", "-o", out, os.path.join(CSRC, tu + ".hip")], stderr=subprocess.DEVNULL)))
@@ -29,6 +32,12 @@ for out, pr in procs:
             k[2] = int(m.group(1))
 print("%d kernels; scratch bytes / VGPRs / kernel" % len(rows))
 for k, sc, v in sorted(rows):
-    m = re.search(r"ILi(\d)ELi(\d)ELi(\d)ELb(\d)ELi(\d+)E", k)
+    m = re.search(r"scan_kernelILi(\d)ELi(\d)ELi(\d)ELb(\d)ELi(\d+)E", k)
     if m and (sc > 0 or "--all" in sys.argv):
         print("%4d %4d  %-11s cw%s %-8s %-5s tile %s" % (sc, v, names[m.group(1)], m.group(2), modes[m.group(3)], "guard" if m.group(4) == "1" else "full", m.group(5)))
+# the packed-rows kernels are always listed, spilling or not
+print("packed-rows kernels (needle_packed.h): scratch bytes / VGPRs / kernel / LDS window per wave")
+for k, sc, v in sorted(rows):
+    m = re.search(r"packed_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d+)ELb(\d)E", k)
+    if m:
+        print("%4d %4d  %-11s cw%s %-8s %-7s window %5d B" % (sc, v, names[m.group(1)], m.group(2), modes[m.group(3)], "lengths" if m.group(5) == "1" else "", 64 * int(m.group(4))))
