@@ -279,6 +279,31 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         return bitmap;
     }
 
+    /**
+     * Every non-overlapping match of every haystack -- the reference's repeated Matcher.find() on each string -- with the
+     * strings flattened as in {@link #findBatch}: a counting call sizes the result, a second call files it.  Match k of
+     * haystack i is [start[j], end[j]) for j = offsets[i] + k.
+     */
+    public Matches findAllStrings(String[] haystacks) {
+        long[] offsets = new long[haystacks.length + 1];
+        for (int i = 0; i < haystacks.length; i++) {
+            offsets[i + 1] = offsets[i] + haystacks[i].length();
+        }
+        char[] data = new char[(int) offsets[haystacks.length]];
+        for (int i = 0; i < haystacks.length; i++) {
+            haystacks[i].getChars(0, haystacks[i].length(), data, (int) offsets[i]);
+        }
+        long[] matchOffsets = new long[haystacks.length + 1];
+        long[] total = new long[1];
+        check(Native.findAllPackedHost(handle, data, offsets, matchOffsets, null, null, total), null);
+        int[] start = new int[(int) total[0]];
+        int[] end = new int[(int) total[0]];
+        if (total[0] > 0) {
+            check(Native.findAllPackedHost(handle, data, offsets, matchOffsets, start, end, total), null);
+        }
+        return new Matches(matchOffsets, start, end);
+    }
+
     @Override
     public void close() {
         if (handle != 0) {

@@ -51,6 +51,12 @@ final class Native {
      */
     static native int packedHost(long handle, int op, char[] data, long[] offsets, long[] bitmap, int[] start, int[] end);
 
+    /**
+     * needle_find_all_csr_packed_host: every non-overlapping match of every packed haystack (UTF-16 code units back to back +
+     * offsets[n + 1]); matchOffsets long[n + 1]; start / end int[capacity] (null: count only); total long[1].
+     */
+    static native int findAllPackedHost(long handle, char[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end, long[] total);
+
     /** needle_find_all_host: counts int[nRows]; start / end int[nRows * maxPerRow]; more int[1]. */
     static native int findAllHost(long handle, java.nio.ByteBuffer rows, int charWidth, long nRows, long rowStride, int rowLen,
                                   java.nio.ByteBuffer lengths, int maxPerRow, int[] counts, int[] start, int[] end, int[] more);

@@ -313,6 +313,38 @@ NATIVE(jint, packedHost)(JNIEnv *env, jclass c, jlong h, jint op, jcharArray dat
     return rc;
 }
 
+/* needle_find_all_csr_packed_host: data + offsets as packedHost; matchOffsets long[n + 1]; start / end int[capacity] (may be null:
+ * count only); total long[1]. */
+NATIVE(jint, findAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data, jlongArray offsets, jlongArray matchOffsets, jintArray start, jintArray end, jlongArray total) {
+    if (!data || !offsets || !matchOffsets || !total) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, matchOffsets) < n1 || (*env)->GetArrayLength(env, total) < 1) return NEEDLE_ERR_INVALID;
+    jsize cap = start ? (*env)->GetArrayLength(env, start) : 0;
+    if (end && (*env)->GetArrayLength(env, end) < cap) cap = (*env)->GetArrayLength(env, end);
+    if (!end) cap = 0;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong *mo = (*env)->GetLongArrayElements(env, matchOffsets, NULL);
+    jint *st = cap ? (*env)->GetIntArrayElements(env, start, NULL) : NULL;
+    jint *en = cap ? (*env)->GetIntArrayElements(env, end, NULL) : NULL;
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    uint64_t t = 0;
+    int rc = needle_find_all_csr_packed_host((const needle_pattern *)(intptr_t)h, &v, (uint64_t *)mo, (int32_t *)st, (int32_t *)en, (uint64_t)cap, &t);
+    jlong jt = (jlong)t;
+    (*env)->SetLongArrayRegion(env, total, 0, 1, &jt);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, matchOffsets, mo, 0);
+    if (st) (*env)->ReleaseIntArrayElements(env, start, st, 0);
+    if (en) (*env)->ReleaseIntArrayElements(env, end, en, 0);
+    return rc;
+}
+
 NATIVE(jbyteArray, serialize)(JNIEnv *env, jclass c, jlong h) {
     size_t need = 0;
     const needle_pattern *p = (const needle_pattern *)(intptr_t)h;

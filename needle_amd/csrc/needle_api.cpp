@@ -2,6 +2,7 @@
 // points, and the single-haystack Matcher mirror.  No CPU matching path exists in this library.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <functional>
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
@@ -20,6 +21,10 @@
 namespace needle {
 hipError_t launch_scan(int op, int char_width, const ScanArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_packed(int op, int char_width, const PackedArgs &a, int n_cus, hipStream_t stream); // needle_packed_find2.hip
+hipError_t launch_packed_find_all(int char_width, const PackedFindAllArgs &a, int n_cus, hipStream_t stream); // needle_packed_find_all2.hip
+bool packed_find_all_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
+int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
+                      const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill); // needle_compact.hip
 bool shape_for_program(const ProgHeader &h, int char_width, int *waves, int *chb, int *tiles_in_f_rows);
 hipError_t launch_find_all(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream); // needle_find_all.hip
 hipError_t launch_find_all_lockstep(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream); // needle_find_all_ls.hip
@@ -1348,6 +1353,284 @@ static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_
 }
 
 // ------------------------------------------------------------------------------------------------
+// Every match of every row of a packed batch (needle_*_packed_dev of find-all; needle_packed_find_all.h)
+// ------------------------------------------------------------------------------------------------
+// The one answer to "does this program take the packed find-all kernel on rows of char_width": a find-all transducer whose program
+// and the windows of at least the smallest shape fit the LDS.  The routing below and needle_pattern_find_all_transducer (what the
+// tests read) both ask it.
+static bool packed_find_all_takes(const ProgHeader &h, int char_width) {
+    int waves = 0, chb = 0;
+    return h.ft_on && packed_find_all_shape(h.lds_bytes, char_width, &waves, &chb);
+}
+
+// The transducer program the packed find-all kernel walks for this pattern and char width (the lengths transducer, else the RUN
+// transducer -- the order of needle_pattern_find_all_transducer), or *tp = nullptr: the pattern goes by conversion.
+static int packed_find_all_program(needle_pattern *p, int cw, const DevProgram **tp, int *n_cus) {
+    *tp = nullptr;
+    int rc = get_program(p, W_FORWARDS, cw, 8, tp, n_cus);
+    if (rc) return rc;
+    if (!*tp && p->t.fixed_len < 0) {
+        rc = get_program(p, W_FORWARDS, cw, 11, tp, n_cus);
+        if (rc) return rc;
+    }
+    if (*tp && !packed_find_all_takes((*tp)->prog.hdr, cw)) *tp = nullptr;
+    return NEEDLE_OK;
+}
+
+static int check_packed_dev(const needle_pattern *p, const needle_packed_view *v) {
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    return NEEDLE_OK;
+}
+
+// One launch of the packed find-all kernel.  more / too_long (optional, host): read back after one synchronisation of the stream.
+static int packed_find_all_launch(const needle_packed_view *v, const DevProgram *tp, int n_cus, uint32_t *d_counts, const uint64_t *d_offsets,
+                                  int32_t *d_start, int32_t *d_end, uint32_t slots, uint32_t *d_blocks, bool count_only, int *more, int *too_long,
+                                  hipStream_t stream) {
+    PackedFindAllArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f.s.rows = (const uint8_t *)v->data;
+    a.f.s.n_rows = v->n_rows;
+    a.f.s.prog = tp->d_blob;
+    a.f.s.hdr = tp->prog.hdr;
+    a.f.s.fixed_len = -1;
+    a.f.counts = d_counts;
+    a.f.offsets = d_offsets;
+    a.f.starts = d_start;
+    a.f.ends = d_end;
+    a.f.slots = slots;
+    a.f.packed = d_blocks;
+    a.f.kshift = d_blocks ? 6u : 0u;
+    a.f.count_only = count_only ? 1u : 0u;
+    a.row_offsets = v->offsets;
+    int32_t *d_flags = nullptr; // [0] more, [1] too long
+    HIP_TRY(scratch_malloc((void **)&d_flags, 16, stream));
+    a.f.more = d_flags;
+    a.too_long = d_blocks ? d_flags + 1 : nullptr;
+    hipError_t e = hipMemsetAsync(d_flags, 0, 8, stream);
+    if (e == hipSuccess) e = launch_packed_find_all((int)v->char_width, a, n_cus, stream);
+    int32_t h[2] = {0, 0};
+    if (e == hipSuccess && (more || too_long)) { // the only synchronisation: the caller asked whether its slots sufficed
+        e = hipMemcpyAsync(h, d_flags, 8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    }
+    (void)scratch_free(d_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "find_all (packed kernel)");
+    if (more) *more = h[0] != 0;
+    if (too_long) *too_long = h[1] != 0;
+    return NEEDLE_OK;
+}
+
+// Patterns without a packed find-all program: the offsets are read back ONCE (a synchronisation of the stream), consecutive rows are
+// converted chunk by chunk -- each chunk at its own stride, its padded bytes within 4x its text + 64 KiB -- by needle_rows_from_packed_dev
+// and run through the fixed-stride entry.  Per-row counts and absolute CSR offsets need no merge step.
+static int packed_find_all_by_conversion(needle_pattern *p, const needle_packed_view *v, uint32_t *d_counts, const uint64_t *d_offsets,
+                                         int32_t *d_start, int32_t *d_end, int *more, hipStream_t stream) {
+    const uint64_t n = v->n_rows, cw = v->char_width;
+    std::vector<uint64_t> off((size_t)n + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), v->offsets, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    struct Chunk {
+        uint64_t r0, r1, stride_bytes;
+    };
+    std::vector<Chunk> chunks;
+    uint64_t biggest = 0;
+    auto stride_of = [&](uint64_t len) { return std::max<uint64_t>(16, (len * cw + 15) & ~(uint64_t)15); };
+    for (uint64_t r0 = 0; r0 < n;) {
+        uint64_t r1 = r0, longest = 0;
+        while (r1 < n) {
+            if (off[r1 + 1] < off[r1]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
+            const uint64_t l = std::max<uint64_t>(longest, off[r1 + 1] - off[r1]);
+            if (stride_of(l) >= (1ull << 26)) return fail(NEEDLE_ERR_UNSUPPORTED, "rows of 64 MiB or more: not on the packed find-all entries");
+            if (r1 > r0 && (r1 + 1 - r0) * stride_of(l) > 4 * (off[r1 + 1] - off[r0]) * cw + (64u << 10)) break;
+            longest = l;
+            ++r1;
+        }
+        chunks.push_back({r0, r1, stride_of(longest)});
+        biggest = std::max<uint64_t>(biggest, (r1 - r0) * (stride_of(longest) + 4));
+        r0 = r1;
+    }
+    uint8_t *tmp = nullptr; // rows | lengths of the biggest chunk (reused: every chunk runs on the same stream)
+    HIP_TRY(scratch_malloc((void **)&tmp, biggest + 256, stream));
+    auto done = [&](int code) {
+        (void)scratch_free(tmp, stream);
+        return code;
+    };
+    if (more) *more = 0;
+    for (const Chunk &c : chunks) {
+        const uint64_t nr = c.r1 - c.r0;
+        uint32_t *d_len = (uint32_t *)(tmp + ((nr * c.stride_bytes + 255) & ~(uint64_t)255));
+        needle_packed_view sub = *v;
+        sub.offsets = v->offsets + c.r0;
+        sub.n_rows = nr;
+        int rc = needle_rows_from_packed_dev(&sub, tmp, c.stride_bytes / cw, d_len, nullptr, stream);
+        if (rc) return done(rc);
+        needle_batch_view bv;
+        memset(&bv, 0, sizeof(bv));
+        bv.rows = tmp;
+        bv.char_width = v->char_width;
+        bv.n_rows = nr;
+        bv.row_stride = c.stride_bytes / cw;
+        bv.lengths = d_len;
+        int m = 0;
+        rc = d_counts ? needle_count_matches_dev(p, &bv, d_counts + c.r0, stream)
+                      : needle_find_all_csr_dev(p, &bv, d_offsets + c.r0, d_start, d_end, more ? &m : nullptr, stream);
+        if (rc) return done(rc);
+        if (more && m) *more = 1;
+    }
+    return done(NEEDLE_OK);
+}
+
+extern "C" {
+
+int needle_count_matches_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t *d_counts, void *stream_) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    int rc = check_packed_dev(p, v);
+    if (rc) return rc;
+    if (!d_counts) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    const DevProgram *tp = nullptr;
+    int n_cus = 0;
+    rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
+    if (rc) return rc;
+    if (tp) return packed_find_all_launch(v, tp, n_cus, d_counts, nullptr, nullptr, nullptr, 0, nullptr, true, nullptr, nullptr, (hipStream_t)stream_);
+    return packed_find_all_by_conversion(p, v, d_counts, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+}
+
+int needle_find_all_csr_packed_dev(const needle_pattern *cp, const needle_packed_view *v, const uint64_t *d_offsets, int32_t *d_start,
+                                   int32_t *d_end, int *more, void *stream_) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    int rc = check_packed_dev(p, v);
+    if (rc) return rc;
+    if (!d_offsets || !d_start || !d_end) return fail(NEEDLE_ERR_INVALID, "offsets / output buffer is NULL");
+    if (more) *more = 0;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    const DevProgram *tp = nullptr;
+    int n_cus = 0;
+    rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
+    if (rc) return rc;
+    if (tp) return packed_find_all_launch(v, tp, n_cus, nullptr, d_offsets, d_start, d_end, 0, nullptr, false, more, nullptr, (hipStream_t)stream_);
+    return packed_find_all_by_conversion(p, v, nullptr, d_offsets, d_start, d_end, more, (hipStream_t)stream_);
+}
+
+int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t max_per_row, uint64_t *d_offsets,
+                                         uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, int *more, void *stream_) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    int rc = check_packed_dev(p, v);
+    if (rc) return rc;
+    if (!d_offsets || !d_total || (cap && !d_start_end16)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (max_per_row == 0 || max_per_row > 4096) return fail(NEEDLE_ERR_INVALID, "max_per_row must be 1 .. 4096");
+    if (more) *more = 0;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    const DevProgram *tp = nullptr;
+    int n_cus = 0;
+    rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
+    if (rc) return rc;
+    if (!tp)
+        return fail(NEEDLE_ERR_UNSUPPORTED, "needle_find_all_compact16_packed_dev: the pattern has no find-all transducer for these rows (use "
+                                            "needle_count_matches_packed_dev + needle_find_all_csr_packed_dev)");
+    hipStream_t stream = (hipStream_t)stream_;
+    int too_long = 0;
+    rc = compact_blocked16(v->n_rows, max_per_row, d_offsets, d_start_end16, cap, d_total, stream, [&](uint32_t *counts, uint32_t *blocks) {
+        return packed_find_all_launch(v, tp, n_cus, counts, nullptr, nullptr, nullptr, max_per_row, blocks, false, more, more ? &too_long : nullptr, stream);
+    });
+    if (rc) return rc;
+    if (too_long) return fail(NEEDLE_ERR_UNSUPPORTED, "needle_find_all_compact16_packed_dev: rows of at most 65 535 chars (a longer row's matches were not filed)");
+    return NEEDLE_OK;
+}
+
+// The packed batch in host memory: row chunks of at most NEEDLE_HOST_CHUNK_BYTES of text are uploaded (their offsets rebased to the
+// chunk), counted, the prefix sum built here, filled (in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of results) and downloaded.
+int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
+                                    uint64_t capacity, uint64_t *total) {
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!offsets || !total || (capacity && (!start || !end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    offsets[0] = 0;
+    *total = 0;
+    const uint64_t n = v->n_rows, cw = v->char_width;
+    if (n == 0) return NEEDLE_OK;
+    for (uint64_t r = 0; r < n; ++r)
+        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
+    if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
+    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
+    static const uint64_t kResultBytes = getenv("NEEDLE_HOST_RESULT_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_RESULT_BYTES")) : (512ull << 20);
+    const uint64_t max_m = std::max<uint64_t>(kResultBytes / 8, 1);
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    std::vector<uint64_t> local;
+    std::vector<uint32_t> counts;
+    for (uint64_t r0 = 0; r0 < n;) {
+        uint64_t r1 = r0 + 1; // at least one row; then while the chunk's text + 12 bytes per row stay within the budget
+        while (r1 < n && (v->offsets[r1 + 1] - v->offsets[r0]) * cw + (r1 + 1 - r0) * 12 <= kHostChunkBytes) ++r1;
+        const uint64_t nr = r1 - r0, c0 = v->offsets[r0], text = (v->offsets[r1] - c0) * cw;
+        uint8_t *d = nullptr, *d_out = nullptr; // data | offsets | counts | CSR offsets;  start | end
+        const uint64_t o_off = up16(std::max<uint64_t>(text, 4)), o_cnt = o_off + up16((nr + 1) * 8), o_csr = o_cnt + up16(nr * 4),
+                       all = o_csr + up16((nr + 1) * 8);
+        HIP_TRY(hipMalloc((void **)&d, all));
+        auto done = [&](int code) {
+            (void)hipFree(d);
+            if (d_out) (void)hipFree(d_out);
+            return code;
+        };
+        local.resize(nr + 1);
+        for (uint64_t r = 0; r <= nr; ++r) local[r] = v->offsets[r0 + r] - c0;
+        hipError_t e = text ? hipMemcpy(d, (const uint8_t *)v->data + c0 * cw, text, hipMemcpyHostToDevice) : hipSuccess;
+        if (e == hipSuccess) e = hipMemcpy(d + o_off, local.data(), (nr + 1) * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host upload"));
+        needle_packed_view dv = *v;
+        dv.data = d;
+        dv.offsets = (const uint64_t *)(d + o_off);
+        dv.n_rows = nr;
+        rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(d + o_cnt), nullptr);
+        if (rc) return done(rc);
+        counts.resize(nr);
+        e = hipMemcpy(counts.data(), d + o_cnt, nr * 4, hipMemcpyDeviceToHost); // (synchronises with the count pass)
+        if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host counts"));
+        for (uint64_t r = 0; r < nr; ++r) offsets[r0 + r + 1] = offsets[r0 + r] + counts[r];
+        if (offsets[r1] > offsets[r0] && offsets[r1] <= capacity) {
+            uint64_t biggest = 0; // the fill pass in sub-ranges: at least one row, at most max_m matches (one row may exceed it)
+            std::vector<std::pair<uint64_t, uint64_t>> ranges;
+            for (uint64_t a = r0; a < r1;) {
+                uint64_t b = a + 1;
+                while (b < r1 && offsets[b + 1] - offsets[a] <= max_m) ++b;
+                ranges.emplace_back(a, b);
+                biggest = std::max<uint64_t>(biggest, offsets[b] - offsets[a]);
+                a = b;
+            }
+            e = hipMalloc((void **)&d_out, 2 * up16(biggest * 4) + 16);
+            if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host results"));
+            for (const auto &rg : ranges) {
+                const uint64_t a = rg.first, sn = rg.second - rg.first, m = offsets[rg.second] - offsets[a];
+                if (m == 0) continue;
+                local.resize(sn + 1);
+                for (uint64_t r = 0; r <= sn; ++r) local[r] = offsets[a + r] - offsets[a];
+                e = hipMemcpy(d + o_csr, local.data(), (sn + 1) * 8, hipMemcpyHostToDevice);
+                if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host offsets"));
+                needle_packed_view sv = dv;
+                sv.offsets = dv.offsets + (a - r0);
+                sv.n_rows = sn;
+                int more = 0;
+                rc = needle_find_all_csr_packed_dev(p, &sv, (const uint64_t *)(d + o_csr), (int32_t *)d_out, (int32_t *)(d_out + up16(biggest * 4)), &more, nullptr);
+                if (rc) return done(rc);
+                if (more) return done(fail(NEEDLE_ERR_DEVICE, "find_all_csr_packed_host: count pass and fill pass disagree"));
+                e = hipMemcpy(start + offsets[a], d_out, m * 4, hipMemcpyDeviceToHost);
+                if (e == hipSuccess) e = hipMemcpy(end + offsets[a], d_out + up16(biggest * 4), m * 4, hipMemcpyDeviceToHost);
+                if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host download"));
+            }
+        }
+        done(NEEDLE_OK);
+        r0 = r1;
+    }
+    *total = offsets[n];
+    return NEEDLE_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
 extern "C" {
 
 int needle_matches_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, void *s) {
@@ -1693,7 +1976,7 @@ int needle_pattern_find_all_transducer(const needle_pattern *cp, int char_width,
     if (ml) pr = lower_find_all_transducer(p->t, *ml, char_width, max_prog_lds());
     // (no transducer on the lengths automaton: the RUN transducer, if the pattern is one of runs -- info[11] = 2)
     if ((pr.blob.empty() || !pr.hdr.ft_on) && p->t.fixed_len < 0) pr = lower_find_all_runs(p->t, char_width, max_prog_lds());
-    if (pr.blob.empty() || !pr.hdr.ft_on) return NEEDLE_OK;
+    if (pr.blob.empty() || !packed_find_all_takes(pr.hdr, char_width)) return NEEDLE_OK; // (ft_on, and a packed find-all shape fits)
     *available = 1;
     if (info) {
         const ProgHeader &h = pr.hdr;

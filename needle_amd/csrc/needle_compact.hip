@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 #include <string>
 
 #include "../../include/needle_hip.h"
@@ -223,18 +224,12 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint32_t *counts, co
     if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n_rows] = *total;
 }
 
-int find_all_compact16(const needle_pattern *p, const needle_batch_view *v, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16,
-                       uint64_t cap, uint64_t *d_total, int *more, void *stream_) {
-    if (!p || !v) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    if (!d_offsets || !d_total || (cap && !d_start_end16)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    if (max_per_row == 0 || max_per_row > 4096) return fail(NEEDLE_ERR_INVALID, "max_per_row must be 1 .. 4096");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (more) *more = 0;
-    if (v->n_rows == 0) {
-        if (hipMemsetAsync(d_total, 0, 8, stream) != hipSuccess || hipMemsetAsync(d_offsets, 0, 8, stream) != hipSuccess) return fail(NEEDLE_ERR_DEVICE, "hipMemsetAsync");
-        return NEEDLE_OK;
-    }
-    const uint64_t n = v->n_rows, n_groups = (n + 63) / 64;
+// The compaction of group-blocked one-dword slots into offsets + a dense match array, for any producer of such slots: fill(counts, blocks)
+// files every row's matches (n_rows counts, (n_rows + 63) / 64 x max_per_row x 64 dwords of slots, both in library scratch) on `stream`.
+// Used by needle_find_all_compact16_dev (fixed-stride rows) and needle_find_all_compact16_packed_dev (packed rows: the same 64-row groups).
+int compact16_from_blocks(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total,
+                          hipStream_t stream, const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill) {
+    const uint64_t n_groups = (n + 63) / 64;
     const uint32_t n_blocks = (uint32_t)((n_groups + kWordsPerBlock - 1) / kWordsPerBlock);
     auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
     const uint64_t o_blocks = up(n * 4), o_gsum = o_blocks + up(n_groups * (uint64_t)max_per_row * 256), o_goff = o_gsum + up(n_groups * 4),
@@ -248,8 +243,7 @@ int find_all_compact16(const needle_pattern *p, const needle_batch_view *v, uint
     uint32_t *counts = (uint32_t *)tmp, *blocks = (uint32_t *)(tmp + o_blocks), *gsum = (uint32_t *)(tmp + o_gsum), *goff = (uint32_t *)(tmp + o_goff),
              *bsum = (uint32_t *)(tmp + o_bsum);
     uint64_t *boff = (uint64_t *)(tmp + o_boff);
-    // (more == NULL: no synchronisation -- a row with more than max_per_row matches is then silently cut, as in the dense forms)
-    const int rc = needle_find_all_blocked16_dev(p, v, max_per_row, counts, blocks, more, stream_);
+    const int rc = fill(counts, blocks);
     if (rc) return done(rc);
     const unsigned grid = (unsigned)std::min<uint64_t>((n_groups + 3) / 4, 4096);
     hipLaunchKernelGGL(group_sum_kernel, dim3(grid), dim3(256), 0, stream, counts, n, n_groups, gsum);
@@ -260,6 +254,23 @@ int find_all_compact16(const needle_pattern *p, const needle_batch_view *v, uint
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return done(fail(NEEDLE_ERR_DEVICE, std::string("compact find-all kernels: ") + hipGetErrorString(e)));
     return done(NEEDLE_OK);
+}
+
+int find_all_compact16(const needle_pattern *p, const needle_batch_view *v, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16,
+                       uint64_t cap, uint64_t *d_total, int *more, void *stream_) {
+    if (!p || !v) return fail(NEEDLE_ERR_INVALID, "NULL argument");
+    if (!d_offsets || !d_total || (cap && !d_start_end16)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (max_per_row == 0 || max_per_row > 4096) return fail(NEEDLE_ERR_INVALID, "max_per_row must be 1 .. 4096");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (more) *more = 0;
+    if (v->n_rows == 0) {
+        if (hipMemsetAsync(d_total, 0, 8, stream) != hipSuccess || hipMemsetAsync(d_offsets, 0, 8, stream) != hipSuccess) return fail(NEEDLE_ERR_DEVICE, "hipMemsetAsync");
+        return NEEDLE_OK;
+    }
+    // (more == NULL: no synchronisation -- a row with more than max_per_row matches is then silently cut, as in the dense forms)
+    return compact16_from_blocks(v->n_rows, max_per_row, d_offsets, d_start_end16, cap, d_total, stream, [&](uint32_t *counts, uint32_t *blocks) {
+        return needle_find_all_blocked16_dev(p, v, max_per_row, counts, blocks, more, stream_);
+    });
 }
 
 // ---- host batches: chunks of at most ~2 GiB of rows resident at a time (64-row boundaries: whole bitmap words)
@@ -316,6 +327,14 @@ uint64_t rows_per_chunk(const needle_batch_view *v) {
 }
 
 } // namespace
+
+namespace needle {
+// (the compaction, for needle_api.cpp's packed-rows entries)
+int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
+                      const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill) {
+    return compact16_from_blocks(n, max_per_row, d_offsets, d_start_end16, cap, d_total, stream, fill);
+}
+} // namespace needle
 
 extern "C" {
 

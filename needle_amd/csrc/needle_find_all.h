@@ -1,5 +1,5 @@
-// Launch arguments of the one-pass find-all kernel (needle_find_all.hip); shared with the launcher's caller in
-// needle_api.cpp.
+// Launch arguments of the one-pass find-all kernels (needle_find_all.hip, needle_find_all_ls.hip, needle_packed_find_all.h); shared
+// with the launchers' caller in needle_api.cpp.
 #pragma once
 #include <stddef.h>
 #include "needle_device.h"
@@ -30,6 +30,15 @@ struct FindAllArgs {
 };
 // backward_walk (needle_walk.h) reads the ScanArgs header words from the kernarg segment at their offsets INSIDE ScanArgs: it must be the first member
 static_assert(offsetof(FindAllArgs, s) == 0, "ScanArgs must be the first member of FindAllArgs (kernarg_here, needle_walk.h)");
+
+// Every non-overlapping match of every row of a PACKED batch in one pass (needle_packed_find_all.h).
+struct PackedFindAllArgs {
+    FindAllArgs f;                 // FIRST member.  Used: s.rows (the view's data), s.n_rows, s.prog / s.hdr; counts, starts, ends,
+                                   // packed, more, offsets (CSR), count_only, slots and kshift (0, or 6 with packed: group-blocked)
+    const uint64_t *row_offsets;   // the view's offsets: n_rows + 1 entries (device)
+    int32_t *too_long;             // group-blocked one-dword form: set to 1 when a row has more than 65 535 chars (nothing is filed
+                                   // for it, its count is 0)
+};
 
 
 } // namespace needle

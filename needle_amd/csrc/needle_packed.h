@@ -39,11 +39,145 @@
 
 namespace needle {
 
+// ------------------------------------------------------------------------------------------------
+// The staging shared by the packed-rows kernels (packed_kernel below, packed_find_all_kernel in needle_packed_find_all.h)
+// ------------------------------------------------------------------------------------------------
+// A wave's LDS window: 64 slots of CHB bytes, slot_stride apart (the tile scan_kernel's wave would use).  in_f_rows: the first
+// four waves' slots lie in the upper 128 B of F rows wave*64 .. wave*64+63 (scan programs only; 0 for every other program).
+template <int CHB>
+struct PackedWindow {
+    uint32_t base, slot_stride;
+    __device__ __forceinline__ PackedWindow(uint32_t prog_lds_bytes, uint32_t in_f_rows, int wave) {
+        if (in_f_rows && wave < 4) {
+            base = kLdsF1 + (uint32_t)wave * 64u * 256u + 128u;
+            slot_stride = 256u;
+        } else {
+            const uint32_t first = in_f_rows ? 4u : 0u;
+            base = ((prog_lds_bytes + 15u) & ~15u) + ((uint32_t)wave - first) * (64u * CHB);
+            slot_stride = CHB;
+        }
+    }
+    // LDS address of window byte bo (a 16-byte block never straddles slots)
+    __device__ __forceinline__ uint32_t at(uint32_t bo) const { return base + (bo / CHB) * slot_stride + (bo % CHB); }
+};
+
+__device__ __forceinline__ uint64_t packed_lane_u64(uint64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return (uint64_t)hi << 32 | lo;
+}
+
+// Streams every group of this wave (persistent: groups wave, wave + wave_cnt, ...) through its window.  Per group, with rs / re =
+// the lane's row as absolute byte addresses [rs, re) (rows past n_rows: empty, at the batch's end):
+//   begin_group(grp)   the lane's per-row state
+//   walk_window(w)     the window at absolute address w (128-byte aligned, kWin bytes) is in LDS: walk the lane's part of it
+//   unresolved()       the lane's row still wants text (a row also stops wanting it at its end)
+//   finish_rows(grp)   the group's results
+template <int CW, int CHB, class BeginGroup, class WalkWindow, class Unresolved, class FinishRows>
+__device__ __forceinline__ void packed_stream(int lane, int wave, int n_waves, const uint8_t *rows, const uint64_t *offsets, uint64_t n_rows,
+                                              const PackedWindow<CHB> &win, uint64_t &rs, uint64_t &re, BeginGroup &&begin_group, WalkWindow &&walk_window,
+                                              Unresolved &&unresolved, FinishRows &&finish_rows) {
+    constexpr uint32_t kWin = 64u * CHB;      // window bytes per wave
+    constexpr int kLoads = CHB / 16;          // 16-byte loads per lane per window
+    const uint64_t n_groups = (n_rows + 63) >> 6;
+    const uint64_t wave_cnt = (uint64_t)gridDim.x * n_waves;
+    uint64_t g = (uint64_t)blockIdx.x * n_waves + wave;
+    if (g >= n_groups) return;
+    const uint64_t data = (uint64_t)(uintptr_t)rows;
+
+    auto row_bounds = [&](uint64_t grp, uint64_t &b0, uint64_t &b1) __attribute__((always_inline)) {
+        const uint64_t r = (grp << 6) + (uint64_t)lane;
+        const uint64_t i0 = r < n_rows ? r : n_rows;
+        const uint64_t i1 = r + 1 < n_rows ? r + 1 : n_rows;
+        b0 = data + offsets[i0] * CW;
+        b1 = data + offsets[i1] * CW;
+    };
+
+    u32x4 R[kLoads];
+    // Load the window at absolute address w (128-byte aligned) into R: only the 16-byte blocks inside [lo16, hi) -- lo16 = the
+    // span's first byte rounded down to its block -- the rest are zero and never reach a lane's automaton.
+    auto fetch = [&](uint64_t w, uint64_t lo16, uint64_t hi) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < kLoads; ++j) {
+            const uint64_t b = w + (uint64_t)((j * 64 + lane) * 16);
+            u32x4 v = {0, 0, 0, 0};
+            if (b >= lo16 && b < hi) v = load_row16<true>((const uint8_t *)(uintptr_t)b);
+            R[j] = v;
+        }
+    };
+    // Store the window held in R to LDS; with do_fetch, re-issue each register's load for the window at w right behind its
+    // store (as scan_kernel's stage_and_fetch: one window's registers live, loads in flight while the window is walked).
+    auto stage_and_fetch = [&](bool do_fetch, uint64_t w, uint64_t lo16, uint64_t hi) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < kLoads; ++j) {
+            *(lds_u32x4 *)(uintptr_t)win.at((uint32_t)((j * 64 + lane) * 16)) = R[j];
+            asm volatile("" ::: "memory"); // keep store j ahead of load j
+            if (do_fetch) {
+                const uint64_t b = w + (uint64_t)((j * 64 + lane) * 16);
+                u32x4 v = {0, 0, 0, 0};
+                if (b >= lo16 && b < hi) v = load_row16<true>((const uint8_t *)(uintptr_t)b);
+                R[j] = v;
+            }
+            asm volatile("" ::: "memory");
+        }
+    };
+
+    uint64_t span_lo, span_hi;
+    uint64_t nrs = 0, nre = 0; // the next group's rows (loaded while this group is walked)
+    row_bounds(g, rs, re);
+    span_lo = packed_lane_u64(rs, 0);
+    span_hi = packed_lane_u64(re, 63);
+    begin_group(g);
+    bool have = false; // R holds (or has in flight) the current group's first window
+    for (;;) {
+        const uint64_t ng = g + wave_cnt;
+        const bool has_next = ng < n_groups;
+        if (has_next) row_bounds(ng, nrs, nre); // (in flight while this group is walked)
+        bool pf_next = false;                   // the last prefetch was the next group's first window
+        if (span_lo < span_hi) {
+            uint64_t w = span_lo & ~(uint64_t)127;
+            const uint64_t lo16 = span_lo & ~(uint64_t)15;
+            if (!have) fetch(w, lo16, span_hi);
+            for (;;) {
+                const uint64_t wn = w + kWin;
+                const bool same = wn < span_hi; // wave-uniform
+                // prefetch target: this group's next window, else the next group's first one
+                uint64_t pw = wn, plo = lo16, phi = span_hi;
+                if (!same && has_next) {
+                    const uint64_t nlo = packed_lane_u64(nrs, 0);
+                    phi = packed_lane_u64(nre, 63);
+                    pw = nlo & ~(uint64_t)127;
+                    plo = nlo & ~(uint64_t)15;
+                    pf_next = true; // (an empty next span: nothing to load, the predicate below is false everywhere)
+                }
+                stage_and_fetch(same || has_next, pw, plo, phi);
+                asm volatile("" ::: "memory"); // keep the prefetch issued ahead of the walk
+                walk_window(w);
+                const uint64_t live = __ballot(unresolved() && re > wn);
+                if (live == 0ull) break;
+                // the next window starts at the first byte some unresolved row still needs: the lowest live lane's
+                const uint64_t rl = packed_lane_u64(rs, __builtin_ctzll(live));
+                const uint64_t nxt = (rl > wn ? rl : wn) & ~(uint64_t)127;
+                if (nxt != wn) fetch(nxt, lo16, span_hi); // (skipped text of resolved rows)
+                w = nxt;
+            }
+        }
+        finish_rows(g);
+        if (!has_next) break;
+        g = ng;
+        rs = nrs;
+        re = nre;
+        span_lo = packed_lane_u64(rs, 0);
+        span_hi = packed_lane_u64(re, 63);
+        begin_group(g);
+        have = pf_next;
+    }
+}
+
 template <int OP, int CW, int MODE, int CHB, bool LEN>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const PackedArgs pa) {
     const ScanArgs &a = pa.s;
     constexpr uint32_t kWin = 64u * CHB;      // window bytes per wave
-    constexpr int kLoads = CHB / 16;          // 16-byte loads per lane per window
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -85,79 +219,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
     const uint32_t accept_lo = MODE == MODE_PACK ? a.hdr.accept_off : a.hdr.accept_lo;
     const uint32_t start_state = MODE == MODE_PACK ? a.hdr.start_off : a.hdr.start;
 
-    // ---- this wave's LDS window: 64 slots of CHB bytes, slot_stride apart (the tile scan_kernel's wave would use)
-    uint32_t win_base, slot_stride;
-    if (a.tiles_in_f_rows && wave < 4) { // slots in the upper 128 B of F rows wave*64 .. wave*64+63
-        win_base = kLdsF1 + (uint32_t)wave * 64u * 256u + 128u;
-        slot_stride = 256u;
-    } else {
-        const uint32_t first = a.tiles_in_f_rows ? 4u : 0u;
-        win_base = ((a.hdr.lds_bytes + 15u) & ~15u) + ((uint32_t)wave - first) * kWin;
-        slot_stride = CHB;
-    }
-    auto lds_at = [&](uint32_t bo) __attribute__((always_inline)) { // LDS address of window byte bo (a 16-byte block never straddles slots)
-        return win_base + (bo / CHB) * slot_stride + (bo % CHB);
-    };
-
+    const PackedWindow<CHB> win(a.hdr.lds_bytes, a.tiles_in_f_rows, wave);
     const uint64_t n_rows = a.n_rows;
-    const uint64_t n_groups = (n_rows + 63) >> 6;
-    const uint64_t wave_cnt = (uint64_t)gridDim.x * n_waves;
-    uint64_t g = (uint64_t)blockIdx.x * n_waves + wave;
-    if (g >= n_groups) return;
-    const uint64_t data = (uint64_t)(uintptr_t)a.rows;
-
-    // A lane's row as absolute byte addresses [rs, re).  Rows past n_rows are empty (at the batch's end).
-    auto row_bounds = [&](uint64_t grp, uint64_t &rs, uint64_t &re) __attribute__((always_inline)) {
-        const uint64_t r = (grp << 6) + (uint64_t)lane;
-        const uint64_t i0 = r < n_rows ? r : n_rows;
-        const uint64_t i1 = r + 1 < n_rows ? r + 1 : n_rows;
-        rs = data + pa.offsets[i0] * CW;
-        re = data + pa.offsets[i1] * CW;
-    };
-    auto lane_u64 = [](uint64_t v, int l) __attribute__((always_inline)) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-        return (uint64_t)hi << 32 | lo;
-    };
-
-    u32x4 R[kLoads];
-    // Load the window at absolute address w (128-byte aligned) into R: only the 16-byte blocks inside [lo16, hi) -- lo16 = the
-    // span's first byte rounded down to its block -- the rest are zero and never reach a lane's automaton.
-    auto fetch = [&](uint64_t w, uint64_t lo16, uint64_t hi) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < kLoads; ++j) {
-            const uint64_t b = w + (uint64_t)((j * 64 + lane) * 16);
-            u32x4 v = {0, 0, 0, 0};
-            if (b >= lo16 && b < hi) v = load_row16<true>((const uint8_t *)(uintptr_t)b);
-            R[j] = v;
-        }
-    };
-    // Store the window held in R to LDS; with do_fetch, re-issue each register's load for the window at w right behind its
-    // store (as scan_kernel's stage_and_fetch: one window's registers live, loads in flight while the window is walked).
-    auto stage_and_fetch = [&](bool do_fetch, uint64_t w, uint64_t lo16, uint64_t hi) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < kLoads; ++j) {
-            *(lds_u32x4 *)(uintptr_t)lds_at((uint32_t)((j * 64 + lane) * 16)) = R[j];
-            asm volatile("" ::: "memory"); // keep store j ahead of load j
-            if (do_fetch) {
-                const uint64_t b = w + (uint64_t)((j * 64 + lane) * 16);
-                u32x4 v = {0, 0, 0, 0};
-                if (b >= lo16 && b < hi) v = load_row16<true>((const uint8_t *)(uintptr_t)b);
-                R[j] = v;
-            }
-            asm volatile("" ::: "memory");
-        }
-    };
 
     // per-group state
-    uint64_t rs, re, span_lo, span_hi;
-    uint64_t nrs = 0, nre = 0; // the next group's rows (loaded while this group is walked)
+    uint64_t rs, re;           // this lane's row as absolute byte addresses [rs, re) (packed_stream)
     uint32_t st, skip, rem;
     int32_t last_o;            // OP_FIND: lastMatch + skip (origin-relative), -1 = none
     bool row_ok;
     auto begin_group = [&](uint64_t grp) __attribute__((always_inline)) {
-        span_lo = lane_u64(rs, 0);
-        span_hi = lane_u64(re, 63);
         row_ok = ((grp << 6) + (uint64_t)lane) < n_rows;
         skip = (uint32_t)(rs & 15u) / CW;                 // chars of the origin block before the row
         rem = skip + (uint32_t)((re - rs) / CW);          // chars from the origin to the row's end
@@ -177,15 +247,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
             const uint32_t rel = (uint32_t)(w - (rs & ~(uint64_t)15));                            // window start - origin (mod 2^32)
             auto p0_of = [&](uint32_t kb) __attribute__((always_inline)) { return (rel + kb * 16u) / CW; };
             {
-                const u32x4 c = *(const lds_u32x4 *)(uintptr_t)lds_at(kb0 * 16u);
+                const u32x4 c = *(const lds_u32x4 *)(uintptr_t)win.at(kb0 * 16u);
                 const uint32_t wv[4] = {c[0], c[1], c[2], c[3]};
                 walk_piece<OP, CW, MODE, true>(wk, wv, p0_of(kb0), rem, skip, accept_lo, st, last_o);
             }
             if (kb1 > kb0) {
-                u32x4 v = *(const lds_u32x4 *)(uintptr_t)lds_at((kb0 + 1u) * 16u);
+                u32x4 v = *(const lds_u32x4 *)(uintptr_t)win.at((kb0 + 1u) * 16u);
                 for (uint32_t kb = kb0 + 1u; kb < kb1; ++kb) {
                     const uint32_t wv[4] = {v[0], v[1], v[2], v[3]};
-                    v = *(const lds_u32x4 *)(uintptr_t)lds_at((kb + 1u) * 16u); // next block: its latency hides below
+                    v = *(const lds_u32x4 *)(uintptr_t)win.at((kb + 1u) * 16u); // next block: its latency hides below
                     walk_piece<OP, CW, MODE, false>(wk, wv, p0_of(kb), 0u, 0u, accept_lo, st, last_o);
                 }
                 const uint32_t wv[4] = {v[0], v[1], v[2], v[3]};
@@ -218,7 +288,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
             // indexBackwards(end - 1, 0), :536-583, on the row's text in memory (read a moment ago: L2).  No LDS window (0 bytes):
             // every char comes from the row itself, so the walk reads nothing outside it.
             const uint8_t *rowp = (const uint8_t *)(uintptr_t)rs;
-            s = backward_walk<CW>(a, res, last, 0, win_base, 0u, 0u, 0u, rowp);
+            s = backward_walk<CW>(a, res, last, 0, win.base, 0u, 0u, 0u, rowp);
             s = res ? s : -1;
         }
         if (row_ok) {
@@ -228,50 +298,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
         }
     };
 
-    row_bounds(g, rs, re);
-    begin_group(g);
-    bool have = false; // R holds (or has in flight) the current group's first window
-    for (;;) {
-        const uint64_t ng = g + wave_cnt;
-        const bool has_next = ng < n_groups;
-        if (has_next) row_bounds(ng, nrs, nre); // (in flight while this group is walked)
-        bool pf_next = false;                   // the last prefetch was the next group's first window
-        if (span_lo < span_hi) {
-            uint64_t w = span_lo & ~(uint64_t)127;
-            const uint64_t lo16 = span_lo & ~(uint64_t)15;
-            if (!have) fetch(w, lo16, span_hi);
-            for (;;) {
-                const uint64_t wn = w + kWin;
-                const bool same = wn < span_hi; // wave-uniform
-                // prefetch target: this group's next window, else the next group's first one
-                uint64_t pw = wn, plo = lo16, phi = span_hi;
-                if (!same && has_next) {
-                    const uint64_t nlo = lane_u64(nrs, 0);
-                    phi = lane_u64(nre, 63);
-                    pw = nlo & ~(uint64_t)127;
-                    plo = nlo & ~(uint64_t)15;
-                    pf_next = true; // (an empty next span: nothing to load, the predicate below is false everywhere)
-                }
-                stage_and_fetch(same || has_next, pw, plo, phi);
-                asm volatile("" ::: "memory"); // keep the prefetch issued ahead of the walk
-                walk_window(w);
-                const uint64_t live = __ballot(!resolved() && re > wn);
-                if (live == 0ull) break;
-                // the next window starts at the first byte some unresolved row still needs: the lowest live lane's
-                const uint64_t rl = lane_u64(rs, __builtin_ctzll(live));
-                const uint64_t nxt = (rl > wn ? rl : wn) & ~(uint64_t)127;
-                if (nxt != wn) fetch(nxt, lo16, span_hi); // (skipped text of resolved rows)
-                w = nxt;
-            }
-        }
-        finish_rows(g);
-        if (!has_next) break;
-        g = ng;
-        rs = nrs;
-        re = nre;
-        begin_group(g);
-        have = pf_next;
-    }
+    packed_stream<CW, CHB>(lane, wave, n_waves, a.rows, pa.offsets, n_rows, win, rs, re, begin_group, walk_window, [&]() __attribute__((always_inline)) { return !resolved(); },
+                           finish_rows);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -805,6 +805,104 @@ class Pattern:
         words, st, en = self.find_packed(data, offsets)
         return unpack_bitmap(words, len(strings)), st, en
 
+    # ---- every match of every packed row (needle_*_packed_dev of find-all)
+    def _packed_dev_view(self, data, offsets):
+        import torch
+        assert data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), \
+            "data: 1-D uint8 or (u)int16 code units"
+        assert isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.device == data.device, "offsets: on data's device"
+        assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1, \
+            "offsets: 1-D int64, n + 1 entries"
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), offsets.numel() - 1, offsets.data_ptr()
+        return v
+
+    def count_matches_packed(self, data, offsets, stream=None):
+        """needle_count_matches_packed_dev: int32[n_rows], the number of non-overlapping matches of every packed row (device tensors:
+        1-D uint8 | (u)int16 data, int64 offsets[n + 1])."""
+        import torch
+        L = _lib.lib()
+        v = self._packed_dev_view(data, offsets)
+        with torch.cuda.device(data.device):
+            s = torch.cuda.current_stream(data.device).cuda_stream if stream is None else stream
+            counts = torch.empty(v.n_rows, dtype=torch.int32, device=data.device)
+            _check(L.needle_count_matches_packed_dev(self._h, ctypes.byref(v), counts.data_ptr(), s))
+        return counts
+
+    def find_all_packed(self, data, offsets, stream=None):
+        """Every non-overlapping match of every packed row in compact form -> (offsets int64[n_rows + 1], start int32[m], end int32[m]).
+        numpy data + offsets: needle_find_all_csr_packed_host.  Device tensors: count (needle_count_matches_packed_dev), torch cumsum,
+        fill (needle_find_all_csr_packed_dev), all on one stream -- as find_all_csr."""
+        L = _lib.lib()
+        if isinstance(data, np.ndarray) or not (type(data).__module__.startswith("torch") and data.is_cuda):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.int16:
+                data = data.view(np.uint16)
+            assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            v = _lib.PackedView()
+            v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+            out = np.zeros(n + 1, dtype=np.uint64)
+            capacity = max(1024, 2 * n)
+            while True:  # (first with a guessed capacity, then with the exact total)
+                st = np.empty(capacity, dtype=np.int32)
+                en = np.empty(capacity, dtype=np.int32)
+                total = ctypes.c_uint64(0)
+                _check(L.needle_find_all_csr_packed_host(self._h, ctypes.byref(v), out.ctypes.data, st.ctypes.data, en.ctypes.data, capacity,
+                                                         ctypes.byref(total)))
+                if total.value <= capacity:
+                    return out.astype(np.int64), st[:total.value], en[:total.value]
+                capacity = int(total.value)
+        import torch
+        v = self._packed_dev_view(data, offsets)
+        n, dev = v.n_rows, data.device
+        one = torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+        with torch.cuda.device(dev), torch.cuda.stream(one):
+            s = one.cuda_stream
+            counts = self.count_matches_packed(data, offsets, s)
+            out = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(counts, 0, out=out[1:])
+            total = int(out[-1].item())
+            st = torch.empty(total, dtype=torch.int32, device=dev)
+            en = torch.empty(total, dtype=torch.int32, device=dev)
+            if total == 0:
+                return out, st, en
+            more = ctypes.c_int(0)
+            _check(L.needle_find_all_csr_packed_dev(self._h, ctypes.byref(v), out.data_ptr(), st.data_ptr(), en.data_ptr(), ctypes.byref(more), s))
+            assert not more.value, "count pass and fill pass disagree"
+        return out, st, en
+
+    def find_all_compact16_packed(self, data, offsets, max_per_row=32, stream=None, cap=None, want_more=True):
+        """needle_find_all_compact16_packed_dev (device tensors): every match of every packed row in ONE walk of the text -> (offsets
+        int64[n + 1], start_end16 int32[total] (start | end << 16), more: bool or None), as find_all_compact16.  Patterns without a
+        find-all transducer raise (use find_all_packed)."""
+        import torch
+        L = _lib.lib()
+        v = self._packed_dev_view(data, offsets)
+        n, dev = v.n_rows, data.device
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+            out = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            total = torch.zeros(1, dtype=torch.int64, device=dev)
+            cap = int(cap) if cap is not None else max(1024, 8 * n)
+            while True:
+                se = torch.empty(cap, dtype=torch.int32, device=dev)
+                more = ctypes.c_int(0)
+                _check(L.needle_find_all_compact16_packed_dev(self._h, ctypes.byref(v), int(max_per_row), out.data_ptr(), se.data_ptr(), cap,
+                                                              total.data_ptr(), ctypes.byref(more) if want_more else None, s))
+                t = int(total.item()) if n else 0
+                if t <= cap:
+                    return out, se[:t], (bool(more.value) if want_more else None)
+                cap = t
+
+    def find_all_strings(self, strings):
+        """Every non-overlapping match of every str (UTF-16 code units, like java.lang.String) -> list of [(start, end), ...] per string
+        (the find_strings counterpart: pack_strings + find_all_packed)."""
+        data, offsets = pack_strings(strings)
+        off, st, en = self.find_all_packed(data, offsets)
+        return [list(zip(st[off[i]:off[i + 1]].tolist(), en[off[i]:off[i + 1]].tolist())) for i in range(len(strings))]
+
     @staticmethod
     def rows_from_packed(data, offsets, row_stride=None, stream=None):
         """Device tensors: packed code units (1-D uint8 | int16) + int64 offsets[n + 1] -> (rows [n, row_stride],

@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""Every match of every packed row: the packed find-all entries against converting the batch first.  The rows are bench.py's c2r / c3r
+rows (make_pattern / make_rows, per-row lengths (r * 2654435761) % 256 + 1), packed back to back on the device; c2p `[0-9]+` takes the RUN
+transducer, c3p (the 1000-keyword dictionary) the lengths transducer.  Routes, timed by HIP events in one process, ALTERNATING (one step
+of each route per round, W warm-up rounds, then K rounds):
+  (a)  needle_find_all_compact16_packed_dev                     one walk of the packed text (more = NULL: no synchronisation)
+  (a') needle_count_matches_packed_dev + torch cumsum + needle_find_all_csr_packed_dev
+  (b)  needle_rows_from_packed_dev (stride 256) + needle_find_all_compact16_dev on its output
+  (b') the same conversion + needle_count_matches_dev + cumsum + needle_find_all_csr_dev
+  (c)  needle_find_all_compact16_dev on the fixed-stride ragged 256-byte rows
+Per route: matches, a start / end checksum (all must agree), the median ms per step (min / max besides), GB/s over ACTUAL bytes -- chars + 8 B offset per row + result
+bytes (compact16: offsets + 4 B per match; CSR: 4 B count per row + offsets + 8 B per match) -- and that rate's share of 8 TB/s.
+The compact16 routes' scratch (n_rows / 64 x max_per_row x 256 B: 5 GB here) is above the library's default scratch keep (512 MB): this
+script raises NEEDLE_SCRATCH_KEEP_MB (unless set) so that no timed step pays a fresh driver allocation.
+python scripts/find_all_packed_rate.py [--rows N] [--steps K] [--warmup W] [--only c2p,c3p] [--max-per-row M]"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK_GBS = 8000.0
+os.environ.setdefault("NEEDLE_SCRATCH_KEEP_MB", "16384")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--only", default="c2p,c3p")
+    ap.add_argument("--max-per-row", type=int, default=128)
+    args = ap.parse_args()
+    import torch
+    import bench
+    from needle_amd import _lib
+    L = _lib.lib()
+    dev = torch.device("cuda", 0)
+    n = args.rows
+    mpr = args.max_per_row
+    lens = (torch.arange(n, device=dev, dtype=torch.int64) * 2654435761 % 256 + 1)
+    l32 = lens.to(torch.int32)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(lens, 0)
+    col = torch.arange(256, device=dev)[None, :]
+    chars = int(offsets[-1].item())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def check(rc):
+        assert rc == 0, L.needle_last_error()
+
+    for wl in args.only.split(","):
+        base = {"c2p": "c2", "c3p": "c3"}[wl]
+        pattern, what, words = bench.make_pattern(base)
+        h = pattern._h
+        kind = pattern.find_all_transducer(1)["kind"]
+        rows = bench.make_rows(base, words, 0, n, dev)
+        data = torch.empty(chars, dtype=torch.uint8, device=dev)
+        for s in range(0, n, 1 << 20):  # packed slab by slab
+            k = min(1 << 20, n - s)
+            data[int(offsets[s].item()):int(offsets[s + k].item())] = rows[s:s + k][col < lens[s:s + k, None]]
+        pv = _lib.PackedView()
+        pv.data, pv.char_width, pv.n_rows, pv.offsets = data.data_ptr(), 1, n, offsets.data_ptr()
+        conv = torch.empty((n, 256), dtype=torch.uint8, device=dev)
+        conv_len = torch.empty(n, dtype=torch.int32, device=dev)
+        cv = _lib.BatchView()
+        cv.rows, cv.char_width, cv.n_rows, cv.row_stride, cv.row_len, cv.lengths = conv.data_ptr(), 1, n, 256, 256, conv_len.data_ptr()
+        rv = _lib.BatchView()
+        rv.rows, rv.char_width, rv.n_rows, rv.row_stride, rv.row_len, rv.lengths = rows.data_ptr(), 1, n, 256, 256, l32.data_ptr()
+        # the exact total first (one synchronising count), so that no timed step has to synchronise
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        check(L.needle_count_matches_packed_dev(h, ctypes.byref(pv), counts.data_ptr(), stream))
+        m = int(counts.to(torch.int64).sum().item())
+        c_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        c_se = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        c_tot = torch.zeros(1, dtype=torch.int64, device=dev)
+        csr_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        st = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        en = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+
+        def a_compact():
+            check(L.needle_find_all_compact16_packed_dev(h, ctypes.byref(pv), mpr, c_off.data_ptr(), c_se.data_ptr(), m, c_tot.data_ptr(), None, stream))
+
+        def a_csr():
+            check(L.needle_count_matches_packed_dev(h, ctypes.byref(pv), counts.data_ptr(), stream))
+            torch.cumsum(counts, 0, out=csr_off[1:])
+            check(L.needle_find_all_csr_packed_dev(h, ctypes.byref(pv), csr_off.data_ptr(), st.data_ptr(), en.data_ptr(), None, stream))
+
+        def convert():
+            check(L.needle_rows_from_packed_dev(ctypes.byref(pv), conv.data_ptr(), 256, conv_len.data_ptr(), None, stream))
+
+        def b_compact():
+            convert()
+            check(L.needle_find_all_compact16_dev(h, ctypes.byref(cv), mpr, c_off.data_ptr(), c_se.data_ptr(), m, c_tot.data_ptr(), None, stream))
+
+        def b_csr():
+            convert()
+            check(L.needle_count_matches_dev(h, ctypes.byref(cv), counts.data_ptr(), stream))
+            torch.cumsum(counts, 0, out=csr_off[1:])
+            check(L.needle_find_all_csr_dev(h, ctypes.byref(cv), csr_off.data_ptr(), st.data_ptr(), en.data_ptr(), None, stream))
+
+        def c_compact():
+            check(L.needle_find_all_compact16_dev(h, ctypes.byref(rv), mpr, c_off.data_ptr(), c_se.data_ptr(), m, c_tot.data_ptr(), None, stream))
+
+        routes = [("a", a_compact, True), ("a'", a_csr, False), ("b", b_compact, True), ("b'", b_csr, False), ("c", c_compact, True)]
+        sums = {}
+        for tag, fn, compact in routes:  # answers (one step each, buffers cleared first)
+            (c_se if compact else st).fill_(0)
+            if not compact:
+                en.fill_(0)
+            fn()
+            torch.cuda.synchronize()
+            if compact:
+                t = int(c_tot.item())
+                se = c_se[:t].to(torch.int64) & 0xFFFFFFFF
+                sums[tag] = (t, int((se & 0xFFFF).sum().item()) + int((se >> 16).sum().item()))
+            else:
+                sums[tag] = (int(csr_off[-1].item()), int(st.to(torch.int64).sum().item()) + int(en.to(torch.int64).sum().item()))
+        assert len(set(sums.values())) == 1, sums  # every route: the same matches (max_per_row is above every row's count here)
+        steps = {tag: [] for tag, _, _ in routes}
+        ev = {tag: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for tag, _, _ in routes}
+        for r in range(args.warmup + args.steps):
+            for tag, fn, _ in routes:
+                e0, e1 = ev[tag]
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if r >= args.warmup:
+                    steps[tag].append(e0.elapsed_time(e1))
+        # the MEDIAN step (a step now and then takes 10-100x longer on the fixed-stride compact16 routes: the mean would report those)
+        ms = {tag: sorted(v)[len(v) // 2] for tag, v in steps.items()}
+        out = {"workload": wl, "what": what + ", per-row lengths uniform in [1, 256], packed", "transducer": {1: "lengths", 2: "run"}[kind],
+               "rows": n, "chars": chars, "matches": sums["a"][0], "checksum_start_end": sums["a"][1], "max_per_row": mpr}
+        for tag, _, compact in routes:
+            res = (n * 8 + 8) + (m * 4 if compact else n * 4 + m * 8)
+            actual = chars + n * 8 + res
+            out[tag] = {"ms": round(ms[tag], 4), "ms_min": round(min(steps[tag]), 4), "ms_max": round(max(steps[tag]), 4), "GB/s": round(actual / ms[tag] / 1e6, 1),
+                        "share_of_8TBs": round(actual / ms[tag] / 1e6 / HBM_PEAK_GBS, 4), "actual_bytes": actual, "checksum": sums[tag][1]}
+        print(json.dumps(out), flush=True)
+        del rows, data, conv, conv_len, c_se, st, en
+
+
+if __name__ == "__main__":
+    main()

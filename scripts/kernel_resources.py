@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""VGPRs / scratch of every instantiation of the tiled scan kernel and of the packed-rows scan kernel (cross-compiled here, no
+"""VGPRs / scratch of every instantiation of the tiled scan kernel, of the packed-rows scan kernel and of the packed-rows find-all kernel
+(cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
 LDS is the program plus one window (the tile) per wave, sized at launch: listed as the window per wave.
 python scripts/kernel_resources.py [--all]"""
@@ -11,7 +12,8 @@ modes = {"0": "pack", "1": "table8", "2": "table16", "3": "hbm", "4": "pair", "5
 procs = []
 tmp = tempfile.mkdtemp()
 for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", "needle_scan_find2",
-           "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2"):
+           "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2",
+           "needle_packed_find_all1", "needle_packed_find_all2"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
                                          "-S", "-o", out, os.path.join(CSRC, tu + ".hip")], stderr=subprocess.DEVNULL)))
@@ -41,3 +43,8 @@ for k, sc, v in sorted(rows):
     m = re.search(r"packed_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d+)ELb(\d)E", k)
     if m:
         print("%4d %4d  %-11s cw%s %-8s %-7s window %5d B" % (sc, v, names[m.group(1)], m.group(2), modes[m.group(3)], "lengths" if m.group(5) == "1" else "", 64 * int(m.group(4))))
+print("packed-rows find-all kernels (needle_packed_find_all.h): scratch bytes / VGPRs / kernel / LDS window per wave")
+for k, sc, v in sorted(rows):
+    m = re.search(r"packed_find_all_kernelILi(\d)ELi(\d+)ELb(\d)E", k)
+    if m:
+        print("%4d %4d  find-all    cw%s %-8s window %5d B" % (sc, v, m.group(1), "run" if m.group(3) == "1" else "lengths", 64 * int(m.group(2))))
