@@ -280,6 +280,42 @@ public final class GpuPattern implements Pattern, AutoCloseable {
     }
 
     /**
+     * {@link #findBatch} with each haystack's start() / end() as ONE int, startEnd[i] = start | end << 16 (-1: no match), for
+     * haystacks of at most 65 534 chars: half the result bytes come back from the device.  Returns the match bitmap.
+     */
+    public long[] findStrings16(String[] haystacks, int[] startEnd) {
+        long[] offsets = new long[haystacks.length + 1];
+        char[] data = flatten(haystacks, offsets);
+        long[] bitmap = new long[(haystacks.length + 63) / 64];
+        check(Native.findPacked16Host(handle, data, offsets, bitmap, startEnd), null);
+        return bitmap;
+    }
+
+    /**
+     * {@link #findBatch} with each haystack's result as ONE short, startLen[i] = start | (end - start) << 8 (0xFFFF: no match,
+     * 0xFFFE: the match (0, 256)), for haystacks of at most 256 chars: a quarter of the result bytes.  Returns the match bitmap.
+     */
+    public long[] findStrings8(String[] haystacks, short[] startLen) {
+        long[] offsets = new long[haystacks.length + 1];
+        char[] data = flatten(haystacks, offsets);
+        long[] bitmap = new long[(haystacks.length + 63) / 64];
+        check(Native.findPacked8Host(handle, data, offsets, bitmap, startLen), null);
+        return bitmap;
+    }
+
+    /** The haystacks' UTF-16 code units back to back; offsets (haystacks.length + 1 entries) is filled in. */
+    private static char[] flatten(String[] haystacks, long[] offsets) {
+        for (int i = 0; i < haystacks.length; i++) {
+            offsets[i + 1] = offsets[i] + haystacks[i].length();
+        }
+        char[] data = new char[(int) offsets[haystacks.length]];
+        for (int i = 0; i < haystacks.length; i++) {
+            haystacks[i].getChars(0, haystacks[i].length(), data, (int) offsets[i]);
+        }
+        return data;
+    }
+
+    /**
      * Every non-overlapping match of every haystack -- the reference's repeated Matcher.find() on each string -- with the
      * strings flattened as in {@link #findBatch}: a counting call sizes the result, a second call files it.  Match k of
      * haystack i is [start[j], end[j]) for j = offsets[i] + k.

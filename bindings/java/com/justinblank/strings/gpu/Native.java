@@ -57,6 +57,15 @@ final class Native {
      */
     static native int findAllPackedHost(long handle, char[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end, long[] total);
 
+    /**
+     * needle_find_packed16_packed_host / needle_find_packed8_packed_host: find() of every packed haystack with a row's result as
+     * one int (start | end << 16; haystacks of at most 65 534 chars) or one short (start | (end - start) << 8, 0xFFFF no match,
+     * 0xFFFE the match (0, 256); haystacks of at most 256 chars).  Longer haystacks: NEEDLE_ERR_UNSUPPORTED.
+     */
+    static native int findPacked16Host(long handle, char[] data, long[] offsets, long[] bitmap, int[] startEnd);
+
+    static native int findPacked8Host(long handle, char[] data, long[] offsets, long[] bitmap, short[] startLen);
+
     /** needle_find_all_host: counts int[nRows]; start / end int[nRows * maxPerRow]; more int[1]. */
     static native int findAllHost(long handle, java.nio.ByteBuffer rows, int charWidth, long nRows, long rowStride, int rowLen,
                                   java.nio.ByteBuffer lengths, int maxPerRow, int[] counts, int[] start, int[] end, int[] more);

@@ -345,6 +345,40 @@ NATIVE(jint, findAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data,
     return rc;
 }
 
+/* needle_find_packed16_packed_host / needle_find_packed8_packed_host: data + offsets as packedHost; bitmap long[(n + 63) / 64];
+ * the results int[n] (16) or short[n] (8). */
+static jint find_packed_compact_host(JNIEnv *env, jlong h, jcharArray data, jlongArray offsets, jlongArray bitmap, jarray out, int bits) {
+    if (!data || !offsets || !bitmap || !out) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, bitmap) < (n1 - 1 + 63) / 64 || (*env)->GetArrayLength(env, out) < n1 - 1) return NEEDLE_ERR_INVALID;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong *bm = (*env)->GetLongArrayElements(env, bitmap, NULL);
+    void *r = bits == 16 ? (void *)(*env)->GetIntArrayElements(env, (jintArray)out, NULL) : (void *)(*env)->GetShortArrayElements(env, (jshortArray)out, NULL);
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    const needle_pattern *p = (const needle_pattern *)(intptr_t)h;
+    int rc = bits == 16 ? needle_find_packed16_packed_host(p, &v, (uint64_t *)bm, (uint32_t *)r) : needle_find_packed8_packed_host(p, &v, (uint64_t *)bm, (uint16_t *)r);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, bitmap, bm, 0);
+    if (bits == 16) (*env)->ReleaseIntArrayElements(env, (jintArray)out, (jint *)r, 0);
+    else (*env)->ReleaseShortArrayElements(env, (jshortArray)out, (jshort *)r, 0);
+    return rc;
+}
+
+NATIVE(jint, findPacked16Host)(JNIEnv *env, jclass c, jlong h, jcharArray data, jlongArray offsets, jlongArray bitmap, jintArray startEnd) {
+    return find_packed_compact_host(env, h, data, offsets, bitmap, startEnd, 16);
+}
+
+NATIVE(jint, findPacked8Host)(JNIEnv *env, jclass c, jlong h, jcharArray data, jlongArray offsets, jlongArray bitmap, jshortArray startLen) {
+    return find_packed_compact_host(env, h, data, offsets, bitmap, startLen, 8);
+}
+
 NATIVE(jbyteArray, serialize)(JNIEnv *env, jclass c, jlong h) {
     size_t need = 0;
     const needle_pattern *p = (const needle_pattern *)(intptr_t)h;

@@ -17,7 +17,8 @@ EXPORTS = [
     "needle_matcher_matches", "needle_matcher_contained_in", "needle_matcher_find", "needle_matcher_find_range",
     "needle_matcher_start", "needle_matcher_end", "needle_rows_from_packed_dev", "needle_matches_packed_dev", "needle_contained_in_packed_dev", "needle_find_packed_dev", "needle_matches_packed_host",
     "needle_contained_in_packed_host", "needle_find_packed_host", "needle_count_matches_packed_dev", "needle_find_all_csr_packed_dev",
-    "needle_find_all_compact16_packed_dev", "needle_find_all_csr_packed_host",
+    "needle_find_all_compact16_packed_dev", "needle_find_all_csr_packed_host", "needle_find_next_packed_dev", "needle_find_packed16_packed_dev",
+    "needle_find_packed8_packed_dev", "needle_find_packed16_packed_host", "needle_find_packed8_packed_host",
     "needle_multi_create", "needle_multi_destroy", "needle_multi_device_count", "needle_multi_stream", "needle_multi_transport", "needle_multi_scan",
     "needle_multi_sync", "needle_scan_host_multi", "needle_multi_unique_id", "needle_multi_create_rank",
     "needle_multi_all_gather_u64", "needle_multi_gather_i32",
@@ -145,6 +146,11 @@ def lib():
     L.needle_find_all_csr_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, P(I), VP]
     L.needle_find_all_compact16_packed_dev.argtypes = [VP, P(PackedView), ctypes.c_uint32, VP, VP, ctypes.c_uint64, VP, P(I), VP]
     L.needle_find_all_csr_packed_host.argtypes = [VP, P(PackedView), VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]
+    L.needle_find_next_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP, VP]
+    L.needle_find_packed16_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP]
+    L.needle_find_packed8_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP]
+    L.needle_find_packed16_packed_host.argtypes = [VP, P(PackedView), VP, VP]
+    L.needle_find_packed8_packed_host.argtypes = [VP, P(PackedView), VP, VP]
     L.needle_matcher_create.argtypes = [VP, VP, ctypes.c_size_t, P(VP)]
     L.needle_matcher_destroy.argtypes = [VP]
     L.needle_matcher_destroy.restype = None

@@ -1300,16 +1300,20 @@ static int run_packed_host_one(const needle_pattern *p, int op, const needle_pac
 
 // Packed device batches scanned as they lie (needle_packed.h): no conversion to fixed-stride rows, no host synchronisation.  The
 // program is chosen as run_dev's scan-kernel path chooses it -- the lengths form where find_lengths_for() allows it, else the
-// backward program -- so that one lowering serves both layouts and the answers are the same.
+// backward program -- so that one lowering serves both layouts and the answers are the same.  That is also the program run_dev
+// walks for per-row cursors (needle_find_next_dev: none of its filters or stripe paths take cursors).
+// find() only: d_from = per-row cursors (needle_find_next_packed_dev); d_packed = the result as one dword per row, or one uint16 with
+// packed8 (needle_find_packed{16,8}_packed_dev: start / end are not used), d_overflow = optional flag of rows that escaped that form.
 static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_view *v, uint64_t *d_bitmap, int32_t *d_start,
-                          int32_t *d_end, void *stream) {
+                          int32_t *d_end, void *stream, const int32_t *d_from = nullptr, uint32_t *d_packed = nullptr, bool packed8 = false,
+                          int32_t *d_overflow = nullptr) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
     int rc = check_packed(v);
     if (rc) return rc;
     if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
     if (!d_bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
-    if (op == OP_FIND && (!d_start || !d_end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
+    if (op == OP_FIND && !d_packed && (!d_start || !d_end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
     if (v->n_rows == 0) return NEEDLE_OK;
     const int which = op == OP_MATCHES ? W_MATCHES : op == OP_CONTAINED_IN ? W_CONTAINED_IN : W_FORWARDS;
     const int cw = (int)v->char_width;
@@ -1347,6 +1351,12 @@ static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_
     a.s.bitmap = d_bitmap;
     a.s.start = d_start;
     a.s.end = d_end;
+    if (op == OP_FIND) {
+        a.s.from = d_from;
+        a.s.packed = d_packed;
+        a.s.packed8 = packed8 ? 1u : 0u;
+        a.overflow = d_packed ? d_overflow : nullptr;
+    }
     a.offsets = v->offsets;
     HIP_TRY(launch_packed(op, cw, a, n_cus, (hipStream_t)stream));
     return NEEDLE_OK;
@@ -1541,6 +1551,47 @@ int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_
     return NEEDLE_OK;
 }
 
+} // extern "C"
+
+// The chunking of the packed HOST entries (needle_find_all_csr_packed_host, needle_find_packed{16,8}_packed_host): consecutive rows
+// [r0, r1), at least `align` rows (or the rest), grown `align` rows at a time while the chunk's text + per_row bytes per row stay within
+// NEEDLE_HOST_CHUNK_BYTES.
+static std::vector<std::pair<uint64_t, uint64_t>> packed_host_chunks(const needle_packed_view *v, uint64_t per_row, uint64_t align) {
+    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
+    const uint64_t n = v->n_rows, cw = v->char_width;
+    auto cost = [&](uint64_t r0, uint64_t r1) { return (v->offsets[r1] - v->offsets[r0]) * cw + (r1 - r0) * per_row; };
+    std::vector<std::pair<uint64_t, uint64_t>> chunks;
+    for (uint64_t r0 = 0; r0 < n;) {
+        uint64_t r1 = std::min<uint64_t>(r0 + align, n);
+        while (r1 < n && cost(r0, std::min<uint64_t>(r1 + align, n)) <= kHostChunkBytes) r1 = std::min<uint64_t>(r1 + align, n);
+        chunks.emplace_back(r0, r1);
+        r0 = r1;
+    }
+    return chunks;
+}
+
+// Upload chunk [r0, r1) of a packed host batch: its text to d_data, its offsets rebased to the chunk's first char to d_offsets (the
+// caller's own when that is char 0; `local` holds the rebased copy).  *dv: the chunk as a device view.
+static hipError_t upload_packed_chunk(const needle_packed_view *v, uint64_t r0, uint64_t r1, uint8_t *d_data, uint64_t *d_offsets,
+                                      std::vector<uint64_t> &local, needle_packed_view *dv) {
+    const uint64_t nr = r1 - r0, cw = v->char_width, c0 = v->offsets[r0], text = (v->offsets[r1] - c0) * cw;
+    const uint64_t *off = v->offsets + r0;
+    if (c0) {
+        local.resize(nr + 1);
+        for (uint64_t r = 0; r <= nr; ++r) local[r] = v->offsets[r0 + r] - c0;
+        off = local.data();
+    }
+    hipError_t e = text ? hipMemcpy(d_data, (const uint8_t *)v->data + c0 * cw, text, hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(d_offsets, off, (nr + 1) * 8, hipMemcpyHostToDevice);
+    *dv = *v;
+    dv->data = d_data;
+    dv->offsets = d_offsets;
+    dv->n_rows = nr;
+    return e;
+}
+
+extern "C" {
+
 // The packed batch in host memory: row chunks of at most NEEDLE_HOST_CHUNK_BYTES of text are uploaded (their offsets rebased to the
 // chunk), counted, the prefix sum built here, filled (in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of results) and downloaded.
 int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
@@ -1556,16 +1607,13 @@ int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed
     for (uint64_t r = 0; r < n; ++r)
         if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
     if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
     static const uint64_t kResultBytes = getenv("NEEDLE_HOST_RESULT_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_RESULT_BYTES")) : (512ull << 20);
     const uint64_t max_m = std::max<uint64_t>(kResultBytes / 8, 1);
     auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
     std::vector<uint64_t> local;
     std::vector<uint32_t> counts;
-    for (uint64_t r0 = 0; r0 < n;) {
-        uint64_t r1 = r0 + 1; // at least one row; then while the chunk's text + 12 bytes per row stay within the budget
-        while (r1 < n && (v->offsets[r1 + 1] - v->offsets[r0]) * cw + (r1 + 1 - r0) * 12 <= kHostChunkBytes) ++r1;
-        const uint64_t nr = r1 - r0, c0 = v->offsets[r0], text = (v->offsets[r1] - c0) * cw;
+    for (const auto &chunk : packed_host_chunks(v, 12, 1)) { // (12 bytes per row: offset + count)
+        const uint64_t r0 = chunk.first, r1 = chunk.second, nr = r1 - r0, text = (v->offsets[r1] - v->offsets[r0]) * cw;
         uint8_t *d = nullptr, *d_out = nullptr; // data | offsets | counts | CSR offsets;  start | end
         const uint64_t o_off = up16(std::max<uint64_t>(text, 4)), o_cnt = o_off + up16((nr + 1) * 8), o_csr = o_cnt + up16(nr * 4),
                        all = o_csr + up16((nr + 1) * 8);
@@ -1575,15 +1623,9 @@ int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed
             if (d_out) (void)hipFree(d_out);
             return code;
         };
-        local.resize(nr + 1);
-        for (uint64_t r = 0; r <= nr; ++r) local[r] = v->offsets[r0 + r] - c0;
-        hipError_t e = text ? hipMemcpy(d, (const uint8_t *)v->data + c0 * cw, text, hipMemcpyHostToDevice) : hipSuccess;
-        if (e == hipSuccess) e = hipMemcpy(d + o_off, local.data(), (nr + 1) * 8, hipMemcpyHostToDevice);
+        needle_packed_view dv;
+        hipError_t e = upload_packed_chunk(v, r0, r1, d, (uint64_t *)(d + o_off), local, &dv);
         if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host upload"));
-        needle_packed_view dv = *v;
-        dv.data = d;
-        dv.offsets = (const uint64_t *)(d + o_off);
-        dv.n_rows = nr;
         rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(d + o_cnt), nullptr);
         if (rc) return done(rc);
         counts.resize(nr);
@@ -1622,12 +1664,77 @@ int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed
             }
         }
         done(NEEDLE_OK);
-        r0 = r1;
     }
     *total = offsets[n];
     return NEEDLE_OK;
 }
 
+} // extern "C"
+
+// needle_find_packed{16,8}_packed_host: the offsets checked on the host (a row beyond the form: NEEDLE_ERR_UNSUPPORTED before any
+// device call), then chunks of whole 64-row groups (the bitmap words stay the caller's) of at most NEEDLE_HOST_CHUNK_BYTES of text
+// uploaded with their offsets rebased to the chunk, scanned by needle_find_packed{16,8}_packed_dev where they lie and downloaded --
+// one chunk after the other, no overlap of one chunk's upload with the previous chunk's scan.
+static int run_packed_compact_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, void *out, bool packed8) {
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if (!bitmap || !out) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    const uint64_t n = v->n_rows, cw = v->char_width, limit = packed8 ? 256 : 65534, rb = packed8 ? 2 : 4;
+    for (uint64_t r = 0; r < n; ++r) {
+        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
+        if (v->offsets[r + 1] - v->offsets[r] > limit)
+            return fail(NEEDLE_ERR_UNSUPPORTED, packed8 ? "8-bit start / length: rows of at most 256 chars (use needle_find_packed16_packed_host)"
+                                                        : "16-bit offsets: rows of at most 65 534 chars (use needle_find_packed_host)");
+    }
+    if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    // whole 64-row groups per chunk (the bitmap words stay the caller's): text + offset + result per row within the budget
+    const std::vector<std::pair<uint64_t, uint64_t>> chunks = packed_host_chunks(v, 8 + rb, 64);
+    uint64_t biggest = 0, max_rows = 0;
+    for (const auto &c : chunks) {
+        biggest = std::max<uint64_t>(biggest, up16(std::max<uint64_t>((v->offsets[c.second] - v->offsets[c.first]) * cw, 4)));
+        max_rows = std::max<uint64_t>(max_rows, c.second - c.first);
+    }
+    // data | offsets | bitmap | results (one buffer for every chunk)
+    const uint64_t o_off = biggest, o_bm = o_off + up16((max_rows + 1) * 8), o_res = o_bm + up16(((max_rows + 63) / 64) * 8),
+                   all = o_res + up16(max_rows * rb);
+    uint8_t *d = nullptr;
+    HIP_TRY(hipMalloc((void **)&d, all));
+    std::vector<uint64_t> local;
+    for (const auto &c : chunks) {
+        const uint64_t r0 = c.first, nr = c.second - c.first;
+        needle_packed_view dv;
+        hipError_t e = upload_packed_chunk(v, r0, c.second, d, (uint64_t *)(d + o_off), local, &dv);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return hip_fail(e, "find_packed_packed_host upload");
+        }
+        rc = packed8 ? needle_find_packed8_packed_dev(p, &dv, (uint64_t *)(d + o_bm), (uint16_t *)(d + o_res), nullptr, nullptr)
+                     : needle_find_packed16_packed_dev(p, &dv, (uint64_t *)(d + o_bm), (uint32_t *)(d + o_res), nullptr, nullptr);
+        if (rc) {
+            (void)hipFree(d);
+            return rc;
+        }
+        e = hipMemcpy(bitmap + r0 / 64, d + o_bm, ((nr + 63) / 64) * 8, hipMemcpyDeviceToHost); // (synchronises with the scan)
+        if (e == hipSuccess) e = hipMemcpy((uint8_t *)out + r0 * rb, d + o_res, nr * rb, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return hip_fail(e, "find_packed_packed_host download");
+        }
+    }
+    (void)hipFree(d);
+    return NEEDLE_OK;
+}
+
+extern "C" {
+int needle_find_packed16_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, uint32_t *start_end16) {
+    return run_packed_compact_host(p, v, bitmap, start_end16, false);
+}
+int needle_find_packed8_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, uint16_t *start_len8) {
+    return run_packed_compact_host(p, v, bitmap, start_len8, true);
+}
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------
@@ -1641,6 +1748,21 @@ int needle_contained_in_packed_dev(const needle_pattern *p, const needle_packed_
 }
 int needle_find_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, int32_t *st, int32_t *en, void *s) {
     return run_packed_dev(p, OP_FIND, v, bm, st, en, s);
+}
+int needle_find_next_packed_dev(const needle_pattern *p, const needle_packed_view *v, const int32_t *cur, uint64_t *bm, int32_t *st,
+                                int32_t *en, void *s) {
+    if (!cur) return fail(NEEDLE_ERR_INVALID, "cursor is NULL");
+    return run_packed_dev(p, OP_FIND, v, bm, st, en, s, cur);
+}
+int needle_find_packed16_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, uint32_t *start_end16,
+                                    int32_t *overflow, void *s) {
+    if (!start_end16) return fail(NEEDLE_ERR_INVALID, "start_end16 is NULL");
+    return run_packed_dev(p, OP_FIND, v, bm, nullptr, nullptr, s, nullptr, start_end16, false, overflow);
+}
+int needle_find_packed8_packed_dev(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, uint16_t *start_len8,
+                                   int32_t *overflow, void *s) {
+    if (!start_len8) return fail(NEEDLE_ERR_INVALID, "start_len8 is NULL");
+    return run_packed_dev(p, OP_FIND, v, bm, nullptr, nullptr, s, nullptr, (uint32_t *)start_len8, true, overflow);
 }
 
 int needle_rows_from_packed_dev(const needle_packed_view *v, void *d_rows, uint64_t row_stride, uint32_t *d_lengths,

@@ -147,9 +147,11 @@ struct ScanArgs {
 // The packed-rows scan kernel (needle_packed.h): rows are code units [offsets[r], offsets[r + 1]) of `s.rows`.
 struct PackedArgs {
     ScanArgs s;               // FIRST member: the backward walk reads the program headers at ScanArgs offsets of the kernarg
-                              // segment.  Used: rows (the view's data), n_rows, prog / hdr, bprog / bhdr, fixed_len,
-                              // tiles_in_f_rows, bitmap, start, end.
+                              // segment.  Used: rows (the view's data), n_rows, from (find(): per-row cursors), prog / hdr,
+                              // bprog / bhdr, fixed_len, tiles_in_f_rows, bitmap, start, end, packed / packed8 (find(): one
+                              // dword / uint16 per row with escapes, pack16_or_over / pack8_or_over below).
     const uint64_t *offsets;  // n_rows + 1 entries (device)
+    int32_t *overflow;        // optional, with s.packed: set to 1 when some row's match escaped its form
 };
 
 // Long rows of table-mode automata (needle_stripe.hip, "speculative stripes"): every stripe is first scanned as a row of
@@ -226,6 +228,19 @@ __host__ __device__ inline uint16_t pack8(int32_t s, int32_t e) {
     if (e < 0) return 0xFFFFu;
     const uint32_t len = (uint32_t)(e - s);
     return len > 255u ? (uint16_t)0xFFFEu : (uint16_t)(((uint32_t)s & 0xFFu) | len << 8);
+}
+// The same forms for PACKED rows (needle_find_packed{16,8}_packed_*), whose lengths the host does not see: the kernel decides per row.
+// A match that the form cannot hold becomes an escape that no held match encodes -- 16-bit: 0xFFFEFFFF (start 0xFFFF > end 0xFFFE,
+// NEEDLE_PACK16_OVER); 8-bit: 0xFFFD (start 253 + length 255 > 256, NEEDLE_PACK8_OVER).  Every other value is pack8's / the dword form's.
+constexpr uint32_t kPack16Over = 0xFFFEFFFFu;
+constexpr uint16_t kPack8Over = 0xFFFDu;
+__host__ __device__ inline uint32_t pack16_or_over(int32_t s, int32_t e) {
+    if (e < 0) return 0xFFFFFFFFu;
+    return e <= 65534 ? (((uint32_t)s & 0xFFFFu) | (uint32_t)e << 16) : kPack16Over;
+}
+__host__ __device__ inline uint16_t pack8_or_over(int32_t s, int32_t e) {
+    if (e < 0) return 0xFFFFu;
+    return e <= 256 ? pack8(s, e) : kPack8Over;
 }
 constexpr uint32_t kLdsF1 = 0, kLdsCmap1 = 0, kLdsTable1 = 512;
 //                  pair mode: cmapA16[256] at 0 (col * n_cols * 2: first char of a pair), cmapB16[256] at 512 (col * 2)

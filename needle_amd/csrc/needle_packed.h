@@ -23,6 +23,11 @@
 //   neither resolved (sink, accepted for containedIn, a dead find() state) nor finished.  Offsets are non-decreasing, so
 //   that is the lowest such LANE's row.  A group whose rows all have their verdict stops reading its span; text of resolved
 //   rows between live ones is skipped a window at a time.
+//   find() variants (template argument EXT, instantiated in translation units of their own so that the plain kernels keep their
+//   registers): per-row cursors (PK_CURSOR, ScanArgs::from, needle_find_next_packed_dev: the walk starts at the cursor's char,
+//   the origin and so the positions stay the row's; 64-byte windows for most 8-bit programs: packed_cursor_narrow), and the result as one dword / uint16 per row with
+//   an escape for matches the form cannot hold (PK_FORMS, ScanArgs::packed / packed8, PackedArgs::overflow:
+//   needle_find_packed{16,8}_packed_dev).
 //   Long rows are correct at one lane's pace (every window of such a row is walked by its one lane).  Intra-row parallelism
 //   for few huge rows stays with the stripe paths of the fixed-stride entries (needle_rows_from_packed_dev first).
 //
@@ -72,11 +77,12 @@ __device__ __forceinline__ uint64_t packed_lane_u64(uint64_t v, int l) {
 //   begin_group(grp)   the lane's per-row state
 //   walk_window(w)     the window at absolute address w (128-byte aligned, kWin bytes) is in LDS: walk the lane's part of it
 //   unresolved()       the lane's row still wants text (a row also stops wanting it at its end)
+//   wanted_from()      the first byte of its row the lane still wants (rs, or where a find() cursor starts the walk)
 //   finish_rows(grp)   the group's results
-template <int CW, int CHB, class BeginGroup, class WalkWindow, class Unresolved, class FinishRows>
+template <int CW, int CHB, class BeginGroup, class WalkWindow, class Unresolved, class WantedFrom, class FinishRows>
 __device__ __forceinline__ void packed_stream(int lane, int wave, int n_waves, const uint8_t *rows, const uint64_t *offsets, uint64_t n_rows,
                                               const PackedWindow<CHB> &win, uint64_t &rs, uint64_t &re, BeginGroup &&begin_group, WalkWindow &&walk_window,
-                                              Unresolved &&unresolved, FinishRows &&finish_rows) {
+                                              Unresolved &&unresolved, WantedFrom &&wanted_from, FinishRows &&finish_rows) {
     constexpr uint32_t kWin = 64u * CHB;      // window bytes per wave
     constexpr int kLoads = CHB / 16;          // 16-byte loads per lane per window
     const uint64_t n_groups = (n_rows + 63) >> 6;
@@ -156,7 +162,7 @@ __device__ __forceinline__ void packed_stream(int lane, int wave, int n_waves, c
                 const uint64_t live = __ballot(unresolved() && re > wn);
                 if (live == 0ull) break;
                 // the next window starts at the first byte some unresolved row still needs: the lowest live lane's
-                const uint64_t rl = packed_lane_u64(rs, __builtin_ctzll(live));
+                const uint64_t rl = packed_lane_u64(wanted_from(), __builtin_ctzll(live));
                 const uint64_t nxt = (rl > wn ? rl : wn) & ~(uint64_t)127;
                 if (nxt != wn) fetch(nxt, lo16, span_hi); // (skipped text of resolved rows)
                 w = nxt;
@@ -174,7 +180,13 @@ __device__ __forceinline__ void packed_stream(int lane, int wave, int n_waves, c
     }
 }
 
-template <int OP, int CW, int MODE, int CHB, bool LEN>
+// find() variants (EXT): the plain int32 pairs (PK_PLAIN, needle_find_packed_dev and matches / containedIn), per-row cursors with
+// int32 pairs (PK_CURSOR, needle_find_next_packed_dev), one dword / uint16 per row with escapes (PK_FORMS,
+// needle_find_packed{16,8}_packed_dev).  Instantiated apart (needle_packed_next*.hip, needle_packed_forms*.hip), so that the
+// plain kernels carry none of the others' registers.
+constexpr int PK_PLAIN = 0, PK_CURSOR = 1, PK_FORMS = 2;
+
+template <int OP, int CW, int MODE, int CHB, bool LEN, int EXT = PK_PLAIN>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const PackedArgs pa) {
     const ScanArgs &a = pa.s;
     constexpr uint32_t kWin = 64u * CHB;      // window bytes per wave
@@ -224,23 +236,59 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
 
     // per-group state
     uint64_t rs, re;           // this lane's row as absolute byte addresses [rs, re) (packed_stream)
-    uint32_t st, skip, rem;
-    int32_t last_o;            // OP_FIND: lastMatch + skip (origin-relative), -1 = none
+    uint32_t st, skip, rem;    // skip: chars from the origin to the walk's first char -- the row's start (PK_CURSOR: its cursor)
+    int32_t last_o;            // OP_FIND: lastMatch + (rs & 15) / CW (origin-relative), -1 = none
     bool row_ok;
     auto begin_group = [&](uint64_t grp) __attribute__((always_inline)) {
-        row_ok = ((grp << 6) + (uint64_t)lane) < n_rows;
-        skip = (uint32_t)(rs & 15u) / CW;                 // chars of the origin block before the row
-        rem = skip + (uint32_t)((re - rs) / CW);          // chars from the origin to the row's end
-        st = start_state;
-        last_o = (OP == OP_FIND && a.hdr.root_accepting) ? (int32_t)skip : -1; // :356, the first iteration's wasAccepted (:440)
+        if constexpr (EXT == PK_CURSOR) {
+            // Matcher.nextStart per row, as scan_kernel's `cursor`: the origin stays the row's first block, so positions stay
+            // row-relative; chars before the cursor take PRE, blocks wholly before it are not walked, an exhausted row (< 0) starts
+            // parked in the sink (find(): `if nextStart == -1 return false`, DFAClassBuilder.java:629-630)
+            const uint64_t r = (grp << 6) + (uint64_t)lane;
+            row_ok = r < n_rows;
+            const uint32_t skip0 = (uint32_t)(rs & 15u) / CW;
+            const uint32_t len = (uint32_t)((re - rs) / CW);
+            rem = skip0 + len;
+            // (the cursor pointer: read from the kernel arguments here, not held in SGPRs through the walk -- kernarg_here, needle_walk.h)
+            const int32_t *const from = kernarg_ptr<const int32_t>(kernarg_here(), (uint32_t)offsetof(ScanArgs, from));
+            const int32_t cur = row_ok ? from[r] : -1;
+            st = cur < 0 ? 0u : start_state;
+            skip = skip0 + (cur > 0 ? (uint32_t)cur : 0u);
+            // :356 literal 0, then the first iteration's wasAccepted (:440) moves it to FROM if FROM < length (as scan_kernel)
+            last_o = (a.hdr.root_accepting && cur >= 0) ? (int32_t)(skip0 + ((uint32_t)cur < len ? (uint32_t)cur : 0u)) : -1;
+        } else {
+            row_ok = ((grp << 6) + (uint64_t)lane) < n_rows;
+            skip = (uint32_t)(rs & 15u) / CW;                 // chars of the origin block before the row
+            rem = skip + (uint32_t)((re - rs) / CW);          // chars from the origin to the row's end
+            st = start_state;
+            last_o = (OP == OP_FIND && a.hdr.root_accepting) ? (int32_t)skip : -1; // :356, the first iteration's wasAccepted (:440)
+        }
     };
     auto resolved = [&]() __attribute__((always_inline)) {
         return OP == OP_CONTAINED_IN ? (st >= accept_lo || st == 0u) : (st <= wk.dead_hi);
     };
+    // the first byte the lane's walk needs: rs, or (PK_CURSOR) its cursor's char, at most re
+    auto wanted_from = [&]() __attribute__((always_inline)) {
+        if constexpr (EXT == PK_CURSOR) {
+            // (recomputed at each use -- the window's first block, the advance after the walk -- rather than held across the walk:
+            // that would cost 2 VGPRs in the kernel's busiest stretch)
+            uint32_t k = skip < rem ? skip : rem;
+            asm volatile("" : "+v"(k));
+            return (rs & ~(uint64_t)15) + (uint64_t)k * CW;
+        } else {
+            return rs;
+        }
+    };
+    // the row still wants text (PK_CURSOR: a cursor at or past the row's end wants none)
+    auto unresolved = [&]() __attribute__((always_inline)) {
+        if constexpr (EXT == PK_CURSOR) return !resolved() && skip < rem;
+        else return !resolved();
+    };
 
-    // Walk the window at w (its bytes are in LDS): this lane's blocks of [max(rs, w), min(re, w + kWin)).
+    // Walk the window at w (its bytes are in LDS): this lane's blocks of [max(wanted_from(), w), min(re, w + kWin)).
     auto walk_window = [&](uint64_t w) __attribute__((always_inline)) {
-        const uint64_t lo = rs > w ? rs : w;
+        const uint64_t from = wanted_from();
+        const uint64_t lo = from > w ? from : w;
         const uint64_t hi = re < w + kWin ? re : w + kWin;
         if (lo < hi && !resolved()) {
             const uint32_t kb0 = (uint32_t)(lo - w) >> 4, kb1 = (uint32_t)(hi - 1u - w) >> 4; // first / last block (window-relative)
@@ -264,10 +312,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
         }
     };
 
-    // Verdicts: the group's bitmap word (one vector store by lane 0) and find()'s start / end per row (DFAClassBuilder.java:640-656).
+    // Verdicts: the group's bitmap word (one vector store by lane 0) and find()'s start / end per row (DFAClassBuilder.java:640-656) --
+    // two int32 arrays, or (PK_FORMS) one dword / uint16 per row with the escapes of pack16_or_over / pack8_or_over.
     auto finish_rows = [&](uint64_t grp) __attribute__((always_inline)) {
         bool res;
-        const int32_t last = last_o >= 0 ? last_o - (int32_t)skip : -1; // row-relative lastMatch
+        const uint32_t skip0 = EXT == PK_CURSOR ? (uint32_t)(rs & 15u) / CW : skip; // chars of the origin block before the row
+        const int32_t last = last_o >= 0 ? last_o - (int32_t)skip0 : -1; // row-relative lastMatch
         if (OP == OP_FIND) res = row_ok && last >= 0;
         else res = row_ok && st >= accept_lo;
         const uint64_t word = __ballot(res);
@@ -285,20 +335,40 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_kernel(const Packe
             }
             s = res ? last - (int32_t)lds_u8(a.hdr.fa_len_off + pidx) : -1;
         } else {
-            // indexBackwards(end - 1, 0), :536-583, on the row's text in memory (read a moment ago: L2).  No LDS window (0 bytes):
-            // every char comes from the row itself, so the walk reads nothing outside it.
+            // indexBackwards(end - 1, FROM), :536-583, on the row's text in memory (read a moment ago: L2).  No LDS window (0 bytes):
+            // every char comes from the row itself, so the walk reads nothing outside it.  FROM: the cursor (PK_CURSOR), else 0.
             const uint8_t *rowp = (const uint8_t *)(uintptr_t)rs;
-            s = backward_walk<CW>(a, res, last, 0, win.base, 0u, 0u, 0u, rowp);
+            s = backward_walk<CW>(a, res, last, EXT == PK_CURSOR ? (int32_t)(skip - skip0) : 0, win.base, 0u, 0u, 0u, rowp);
             s = res ? s : -1;
         }
-        if (row_ok) {
+        if constexpr (EXT == PK_FORMS) {
+            // (the form's words: read from the kernel arguments here, once per group, not held in SGPRs through the walk --
+            // kernarg_here, needle_walk.h)
+            const KernargPtr ka = kernarg_here();
+            uint32_t *const o_packed = kernarg_ptr<uint32_t>(ka, (uint32_t)offsetof(ScanArgs, packed));
+            const bool form8 = kernarg_u32(ka, (uint32_t)offsetof(ScanArgs, packed8)) != 0u;
+            bool over = false; // this row's match does not fit the form
+            if (row_ok) {
+                const uint64_t r = (grp << 6) + (uint64_t)lane;
+                if (form8) {
+                    over = e > 256;
+                    ((uint16_t *)o_packed)[r] = pack8_or_over(s, e);
+                } else {
+                    over = e > 65534;
+                    o_packed[r] = pack16_or_over(s, e);
+                }
+            }
+            int32_t *const o_overflow = kernarg_ptr<int32_t>(ka, (uint32_t)offsetof(PackedArgs, overflow));
+            const uint64_t esc = __ballot(over);
+            if (o_overflow && esc != 0ull && lane == __builtin_ctzll(esc)) *o_overflow = 1; // one store per wave
+        } else if (row_ok) {
             const uint64_t r = (grp << 6) + (uint64_t)lane;
             a.start[r] = s;
             a.end[r] = e;
         }
     };
 
-    packed_stream<CW, CHB>(lane, wave, n_waves, a.rows, pa.offsets, n_rows, win, rs, re, begin_group, walk_window, [&]() __attribute__((always_inline)) { return !resolved(); },
+    packed_stream<CW, CHB>(lane, wave, n_waves, a.rows, pa.offsets, n_rows, win, rs, re, begin_group, walk_window, unresolved, wanted_from,
                            finish_rows);
 }
 
@@ -310,34 +380,46 @@ struct PackedShape {
     size_t lds;
 };
 
-template <int OP, int CW, int MODE, int CHB, bool LEN>
+template <int OP, int CW, int MODE, int CHB, bool LEN, int EXT>
 static hipError_t launch_packed_one(const PackedArgs &a, PackedShape sh, hipStream_t stream) {
-    auto k = packed_kernel<OP, CW, MODE, CHB, LEN>;
+    auto k = packed_kernel<OP, CW, MODE, CHB, LEN, EXT>;
     static thread_local uint64_t configured = 0;
     if (hipError_t e = allow_full_lds((const void *)k, configured); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(sh.grid), dim3(sh.waves * 64), sh.lds, stream, a);
     return hipGetLastError();
 }
 
-template <int OP, int CW, int MODE>
+// The cursor kernels of 8-bit rows in the LDS-table, HBM-table, hot-rows and compressed modes take 64-byte windows only (launch_packed
+// narrows the shape): with 128-byte windows their cursor bookkeeping needs 120-121 VGPRs, above the plain kernels' 119
+// (scripts/kernel_resources.py).  Packed-function and pair-table programs and UTF-16 rows keep the plain kernels' windows.
+constexpr bool packed_cursor_narrow(int cw, uint32_t mode) { return cw == 1 && mode != MODE_PACK && mode != MODE_PAIR; }
+
+template <int OP, int CW, int MODE, int EXT>
 static hipError_t launch_packed_g(const PackedArgs &a, PackedShape sh, hipStream_t s) {
-    if constexpr (OP == OP_FIND && (MODE == MODE_TABLE8 || MODE == MODE_TABLE16 || MODE == MODE_SPARSE || MODE == MODE_PAIR)) {
-        if (a.s.hdr.fa_len_off) // (a "lengths" program: only these modes)
-            return sh.chb == 128 ? launch_packed_one<OP, CW, MODE, 128, true>(a, sh, s) : launch_packed_one<OP, CW, MODE, 64, true>(a, sh, s);
+    if constexpr (EXT == PK_CURSOR && packed_cursor_narrow(CW, MODE)) {
+        if (sh.chb != 64) return hipErrorInvalidValue;
+        if constexpr (MODE == MODE_TABLE8 || MODE == MODE_TABLE16 || MODE == MODE_SPARSE || MODE == MODE_PAIR)
+            if (a.s.hdr.fa_len_off) return launch_packed_one<OP, CW, MODE, 64, true, EXT>(a, sh, s);
+        return launch_packed_one<OP, CW, MODE, 64, false, EXT>(a, sh, s);
+    } else {
+        if constexpr (OP == OP_FIND && (MODE == MODE_TABLE8 || MODE == MODE_TABLE16 || MODE == MODE_SPARSE || MODE == MODE_PAIR)) {
+            if (a.s.hdr.fa_len_off) // (a "lengths" program: only these modes)
+                return sh.chb == 128 ? launch_packed_one<OP, CW, MODE, 128, true, EXT>(a, sh, s) : launch_packed_one<OP, CW, MODE, 64, true, EXT>(a, sh, s);
+        }
+        return sh.chb == 128 ? launch_packed_one<OP, CW, MODE, 128, false, EXT>(a, sh, s) : launch_packed_one<OP, CW, MODE, 64, false, EXT>(a, sh, s);
     }
-    return sh.chb == 128 ? launch_packed_one<OP, CW, MODE, 128, false>(a, sh, s) : launch_packed_one<OP, CW, MODE, 64, false>(a, sh, s);
 }
 
-template <int OP, int CW>
+template <int OP, int CW, int EXT = PK_PLAIN>
 static hipError_t launch_packed_m(const PackedArgs &a, PackedShape sh, hipStream_t s) {
     switch (a.s.hdr.mode) {
-    case MODE_PACK: return launch_packed_g<OP, CW, MODE_PACK>(a, sh, s);
-    case MODE_TABLE8: return launch_packed_g<OP, CW, MODE_TABLE8>(a, sh, s);
-    case MODE_TABLE16: return launch_packed_g<OP, CW, MODE_TABLE16>(a, sh, s);
-    case MODE_PAIR: return CW == 1 ? launch_packed_g<OP, 1, MODE_PAIR>(a, sh, s) : hipErrorInvalidValue; // 8-bit rows only
-    case MODE_HYBRID: return launch_packed_g<OP, CW, MODE_HYBRID>(a, sh, s);
-    case MODE_SPARSE: return launch_packed_g<OP, CW, MODE_SPARSE>(a, sh, s);
-    default: return launch_packed_g<OP, CW, MODE_GLOBAL>(a, sh, s);
+    case MODE_PACK: return launch_packed_g<OP, CW, MODE_PACK, EXT>(a, sh, s);
+    case MODE_TABLE8: return launch_packed_g<OP, CW, MODE_TABLE8, EXT>(a, sh, s);
+    case MODE_TABLE16: return launch_packed_g<OP, CW, MODE_TABLE16, EXT>(a, sh, s);
+    case MODE_PAIR: return CW == 1 ? launch_packed_g<OP, 1, MODE_PAIR, EXT>(a, sh, s) : hipErrorInvalidValue; // 8-bit rows only
+    case MODE_HYBRID: return launch_packed_g<OP, CW, MODE_HYBRID, EXT>(a, sh, s);
+    case MODE_SPARSE: return launch_packed_g<OP, CW, MODE_SPARSE, EXT>(a, sh, s);
+    default: return launch_packed_g<OP, CW, MODE_GLOBAL, EXT>(a, sh, s);
     }
 }
 

@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_find_all_kernel(co
     };
 
     packed_stream<CW, CHB>(lane, wave, n_waves, a.rows, pf.row_offsets, n_rows, win, rs, re, begin_group, walk_window,
-                           []() __attribute__((always_inline)) { return true; }, finish_rows);
+                           []() __attribute__((always_inline)) { return true; }, [&]() __attribute__((always_inline)) { return rs; }, finish_rows);
 }
 
 // Waves per workgroup x window bytes per lane for a transducer program of prog_lds_bytes on rows of char_width (the lock-step kernel's

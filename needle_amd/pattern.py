@@ -21,6 +21,9 @@ UNICODE_CASE = 0x40
 UNICODE_CHARACTER_CLASS = 0x100
 LEFTMOST_LONGEST = 0x800000
 ALL_FLAGS = DOTALL | CASE_INSENSITIVE | UNICODE_CASE | LEFTMOST_LONGEST | UNICODE_CHARACTER_CLASS
+# find() of packed rows in one dword / one uint16 (needle_find_packed{16,8}_packed_*): a match the form cannot hold
+PACK16_OVER = 0xFFFEFFFF
+PACK8_OVER = 0xFFFD
 
 
 class PatternException(RuntimeError):
@@ -804,6 +807,93 @@ class Pattern:
         data, offsets = pack_strings(strings)
         words, st, en = self.find_packed(data, offsets)
         return unpack_bitmap(words, len(strings)), st, en
+
+    def find_next_packed(self, data, offsets, cursor, stream=None):
+        """needle_find_next_packed_dev: one find() step per packed row from cursor[r] (device int32[n_rows]; < 0 = row exhausted) ->
+        (bitmap words, start, end) device tensors, positions relative to the row -- as find_next_batch on the same rows at a fixed
+        stride.  Feeding `end` back as the next cursor enumerates every row's matches."""
+        import torch
+        L = _lib.lib()
+        v = self._packed_dev_view(data, offsets)
+        n = v.n_rows
+        assert isinstance(cursor, torch.Tensor) and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.is_contiguous() and \
+            cursor.numel() >= n, "cursor: device int32[n_rows]"
+        with torch.cuda.device(data.device):
+            s = torch.cuda.current_stream(data.device).cuda_stream if stream is None else stream
+            words = torch.empty((n + 63) // 64, dtype=torch.int64, device=data.device)
+            st = torch.empty(n, dtype=torch.int32, device=data.device)
+            en = torch.empty(n, dtype=torch.int32, device=data.device)
+            _check(L.needle_find_next_packed_dev(self._h, ctypes.byref(v), cursor.data_ptr(), words.data_ptr(), st.data_ptr(), en.data_ptr(), s))
+        return words, st, en
+
+    def _find_compact_packed(self, bits, data, offsets, stream, out):
+        """find_packed16_packed / find_packed8_packed (bits 16 | 8)."""
+        L = _lib.lib()
+        rb = np.uint32 if bits == 16 else np.uint16
+        if isinstance(data, np.ndarray):  # host buffers: needle_find_packed{16,8}_packed_host
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.int16:
+                data = data.view(np.uint16)
+            assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            v = _lib.PackedView()
+            v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+            words = np.zeros((n + 63) // 64, dtype=np.uint64)
+            res = np.zeros(n, dtype=rb)
+            fn = L.needle_find_packed16_packed_host if bits == 16 else L.needle_find_packed8_packed_host
+            _check(fn(self._h, ctypes.byref(v), words.ctypes.data, res.ctypes.data))
+            return words, res
+        import torch
+        v = self._packed_dev_view(data, offsets)
+        n = v.n_rows
+        tdt = torch.int32 if bits == 16 else torch.int16
+        with torch.cuda.device(data.device):
+            s = torch.cuda.current_stream(data.device).cuda_stream if stream is None else stream
+            if out is not None:  # caller-owned (bitmap int64, results int32 | int16, overflow int32 -- zeroed by the caller)
+                words, res, ovf = out
+                assert words.is_cuda and words.dtype == torch.int64 and words.numel() >= (n + 63) // 64
+                assert res.dtype == tdt and res.numel() >= n and ovf.dtype == torch.int32 and ovf.numel() >= 1
+            else:
+                words = torch.empty((n + 63) // 64, dtype=torch.int64, device=data.device)
+                res = torch.empty(n, dtype=tdt, device=data.device)
+                ovf = torch.zeros(1, dtype=torch.int32, device=data.device)
+            fn = L.needle_find_packed16_packed_dev if bits == 16 else L.needle_find_packed8_packed_dev
+            _check(fn(self._h, ctypes.byref(v), words.data_ptr(), res.data_ptr(), ovf.data_ptr(), s))
+        return words, res, ovf
+
+    def find_packed16_packed(self, data, offsets, stream=None, out=None):
+        """find() of every packed row as ONE dword, start | end << 16 (0xFFFFFFFF = no match; NEEDLE_PACK16_OVER = a match ending past
+        65 534).  Device tensors: needle_find_packed16_packed_dev -> (bitmap words, int32[n], overflow int32[1]: 1 when some row
+        escaped); out: optional caller-owned (bitmap, results, zeroed overflow) tensors.  Numpy arrays: needle_find_packed16_packed_host
+        (rows of at most 65 534 chars) -> (bitmap words, uint32[n]).  unpack16_packed() decodes."""
+        return self._find_compact_packed(16, data, offsets, stream, out)
+
+    def find_packed8_packed(self, data, offsets, stream=None, out=None):
+        """find() of every packed row as ONE uint16, pack8's form (start | (end - start) << 8, 0xFFFF = no match, 0xFFFE = (0, 256);
+        NEEDLE_PACK8_OVER = a match ending past 256).  Results as find_packed16_packed (int16 / uint16); the host form takes rows of
+        at most 256 chars.  unpack8_packed() decodes."""
+        return self._find_compact_packed(8, data, offsets, stream, out)
+
+    @staticmethod
+    def unpack16_packed(x):
+        """Entries of find_packed16_packed (any integer dtype holding the bit pattern) -> (start, end, over) numpy arrays: -1 / -1 where
+        there is no match or the match escaped the form (over = True)."""
+        x = np.asarray(x).astype(np.int64) & 0xFFFFFFFF
+        over = x == PACK16_OVER
+        none = (x == 0xFFFFFFFF) | over
+        start = np.where(none, -1, x & 0xFFFF)
+        end = np.where(none, -1, x >> 16)
+        return start.astype(np.int32), end.astype(np.int32), over
+
+    @staticmethod
+    def unpack8_packed(x):
+        """Entries of find_packed8_packed -> (start, end, over) numpy arrays, pack8's escapes decoded as unpack8; -1 / -1 where there
+        is no match or the match escaped the form (over = True)."""
+        x = np.asarray(x).astype(np.int64) & 0xFFFF
+        over = x == PACK8_OVER
+        start, end = Pattern.unpack8(np.where(over, 0xFFFF, x))
+        return start, end, over
 
     # ---- every match of every packed row (needle_*_packed_dev of find-all)
     def _packed_dev_view(self, data, offsets):

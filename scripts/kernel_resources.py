@@ -12,7 +12,8 @@ modes = {"0": "pack", "1": "table8", "2": "table16", "3": "hbm", "4": "pair", "5
 procs = []
 tmp = tempfile.mkdtemp()
 for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", "needle_scan_find2",
-           "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2",
+           "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2", "needle_packed_next1",
+           "needle_packed_next2", "needle_packed_forms1", "needle_packed_forms2",
            "needle_packed_find_all1", "needle_packed_find_all2"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
@@ -40,9 +41,10 @@ for k, sc, v in sorted(rows):
 # the packed-rows kernels are always listed, spilling or not
 print("packed-rows kernels (needle_packed.h): scratch bytes / VGPRs / kernel / LDS window per wave")
 for k, sc, v in sorted(rows):
-    m = re.search(r"packed_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d+)ELb(\d)E", k)
-    if m:
-        print("%4d %4d  %-11s cw%s %-8s %-7s window %5d B" % (sc, v, names[m.group(1)], m.group(2), modes[m.group(3)], "lengths" if m.group(5) == "1" else "", 64 * int(m.group(4))))
+    m = re.search(r"packed_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d+)ELb(\d)ELi(\d)E", k)
+    if m:  # (last template argument: the find() variant -- int32 pairs, per-row cursors, one dword / uint16 per row)
+        print("%4d %4d  %-11s cw%s %-8s %-7s %-7s window %5d B" % (sc, v, names[m.group(1)], m.group(2), modes[m.group(3)], "lengths" if m.group(5) == "1" else "",
+                                                            {"0": "", "1": "cursor", "2": "forms"}[m.group(6)], 64 * int(m.group(4))))
 print("packed-rows find-all kernels (needle_packed_find_all.h): scratch bytes / VGPRs / kernel / LDS window per wave")
 for k, sc, v in sorted(rows):
     m = re.search(r"packed_find_all_kernelILi(\d)ELi(\d+)ELb(\d)E", k)
