@@ -50,6 +50,10 @@ size_t ngram_find_all_lds_bytes(const ProgHeader &h, const NgramParams &ng);
 hipError_t launch_ngram_find_all(const ScanArgs &a, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats, uint32_t slots, uint32_t *counts,
                                  int32_t *starts, int32_t *ends, uint32_t *packed, int32_t *more, const uint64_t *offsets, bool count_only, int n_cus,
                                  hipStream_t stream, int char_width, int page, int sub, uint32_t kshift);
+// needle_ngram_packed_find2.hip: the same filter in front of packed rows (needle_ngram_packed.h)
+size_t ngram_packed_lds_bytes(const ProgHeader &h, const NgramParams &ng);
+hipError_t launch_ngram_packed(int op, const ScanArgs &a, const uint64_t *offsets, int32_t *overflow, const NgramParams &ng, const uint32_t *d_bitmap,
+                               uint32_t *d_stats, int n_cus, hipStream_t stream, int char_width, int page, int sub);
 int ngram_level(); // needle_lower.cpp (NEEDLE_PREFILTER)
 hipError_t launch_unpack(const void *data, const uint64_t *offsets, uint64_t n_rows, uint32_t cw, void *out,
                          uint64_t stride_bytes, uint32_t *lengths, int32_t *overflow, int n_cus, hipStream_t stream);
@@ -722,6 +726,65 @@ static ScanArgs filter_scan_args(const needle_batch_view *v, uint64_t stride, co
     return a;
 }
 
+// ---- Which filter program serves (pattern, op, char width): ONE choice for fixed-stride rows (run_dev) and packed rows (run_packed_dev).
+// Each function answers for one route; *tp == nullptr: not this route.  The callers add what is theirs: the batch's shape, cursors, the
+// LDS footprint of their kernel, the flood watch.
+// UTF-16 rows of a pattern on ONE page of the BMP: the byte program of that page, the text narrowed on load (utf16_route, narrow16).  Every
+// step is speculative -- lowering and uploading the page's byte programs for a pattern that may have no filter at all -- so a failure
+// means "route unavailable", never an error.
+static void filter_route_utf16_page(needle_pattern *p, int op, int which, bool need_backward, const Utf16Route &u16, const DevProgram **tp_out, int *n_cus) {
+    *tp_out = nullptr;
+    const DevProgram *tp = nullptr;
+    const int cw8 = 1 | (u16.page << 8); // the byte program of the pattern's page
+    if (get_program(p, which, cw8, need_backward ? 2 : 0, &tp, n_cus)) return;
+    bool ok = false;
+    if (tp->prog.hdr.mode == MODE_HYBRID || tp->prog.hdr.mode == MODE_GLOBAL) {
+        if (get_program(p, which, cw8, 9, &tp, nullptr)) return;
+        ok = tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0);
+    } else {
+        bool lengths8 = false;
+        if (need_backward && find_lengths_for(tp->prog.hdr.mode)) {
+            const DevProgram *lp = nullptr;
+            if (get_program(p, W_FORWARDS, cw8, 7, &lp, nullptr)) return;
+            if (lp && !(tp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR)) tp = lp, lengths8 = true;
+        }
+        ok = tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || lengths8 || p->t.fixed_len >= 0);
+    }
+    if (ok) *tp_out = tp;
+}
+// UTF-16 rows of a pattern on SEVERAL pages: the WIDE filter's program (variant 10), where wide_filter_wanted() says so for the ordinary
+// UTF-16 program's mode.
+static int filter_route_wide(needle_pattern *p, int op, int which, const DevProgram **tp_out) {
+    *tp_out = nullptr;
+    const DevProgram *tp = nullptr;
+    int rc = get_program(p, which, 2, 10, &tp, nullptr);
+    if (rc) return rc;
+    if (tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0)) *tp_out = tp;
+    return NEEDLE_OK;
+}
+// 8-bit rows of an automaton that fits the LDS in no form (hot rows + HBM table, or the HBM table alone): the filter with verify walks out
+// of HBM / L2 (variant 9).  allow_unbounded: find() without bounded match lengths may take the forward search automaton + backward walks
+// for the starts (variant 12, *bwp_out = the backward program; NEEDLE_PREFILTER_UNBOUNDED=0: never).
+static int filter_route_hbm(needle_pattern *p, int op, int which, bool need_backward, bool allow_unbounded, const DevProgram **tp_out, const DevProgram **bwp_out) {
+    *tp_out = *bwp_out = nullptr;
+    const DevProgram *tp = nullptr;
+    int rc = get_program(p, which, 1, 9, &tp, nullptr);
+    if (rc) return rc;
+    static const bool unbounded_on = !(getenv("NEEDLE_PREFILTER_UNBOUNDED") && atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) == 0);
+    const DevProgram *bwp = nullptr;
+    if (!tp && op == OP_FIND && need_backward && unbounded_on && allow_unbounded) {
+        rc = get_program(p, which, 1, 12, &tp, nullptr);
+        if (rc) return rc;
+        if (tp) {
+            rc = get_program(p, W_BACKWARDS, 1, 1, &bwp, nullptr);
+            if (rc) return rc;
+            if (!bwp) tp = nullptr;
+        }
+    }
+    if (tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0 || bwp)) *tp_out = tp, *bwp_out = bwp;
+    return NEEDLE_OK;
+}
+
 // d_packed (OP_FIND, needle_find_packed16_dev): a row's start / end go there as one dword, stored by the scan kernel itself;
 // d_start / d_end are not used.  The paths for few long rows (stripes) and the opt-in two-row-set kernel keep their int32
 // arrays: they run into scratch and one pack pass follows.
@@ -762,28 +825,10 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
     const Utf16Route u16 = v->char_width == 2 ? utf16_route(p) : Utf16Route();
     if (v->char_width == 2 && op != OP_MATCHES && !d_from && !d_end_state && !no_backward && ngram_level() > 0 && dict_env == 0 && u16.page >= 0 &&
         v->row_stride * 2 < 8 * (uint64_t)kStripeBytes) do {
-        // (every step of this route is speculative -- lowering and uploading the page's byte programs for a pattern that may have no
-        // filter at all: a failure here means "route unavailable", the UTF-16 kernels below serve the call)
+        // (a failure inside this route means "route unavailable", the UTF-16 kernels below serve the call)
         const DevProgram *tp = nullptr;
-        const int cw8 = 1 | (u16.page << 8); // the byte program of the pattern's page
-        rc = get_program(p, which, cw8, need_backward ? 2 : 0, &tp, &n_cus);
-        if (rc) break;
-        bool ok = false;
-        if (tp->prog.hdr.mode == MODE_HYBRID || tp->prog.hdr.mode == MODE_GLOBAL) {
-            rc = get_program(p, which, cw8, 9, &tp, nullptr);
-            if (rc) break;
-            ok = tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0);
-        } else {
-            bool lengths8 = false;
-            if (need_backward && find_lengths_for(tp->prog.hdr.mode)) {
-                const DevProgram *lp = nullptr;
-                rc = get_program(p, W_FORWARDS, cw8, 7, &lp, nullptr);
-                if (rc) break;
-                if (lp && !(tp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR)) tp = lp, lengths8 = true;
-            }
-            ok = tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || lengths8 || p->t.fixed_len >= 0);
-        }
-        if (ok) {
+        filter_route_utf16_page(p, op, which, need_backward, u16, &tp, &n_cus);
+        if (tp) {
             const ScanArgs a = filter_scan_args(v, v->row_stride /* chars */, tp, op == OP_FIND ? p->t.fixed_len : -1, d_bitmap, d_start, d_end, d_packed, packed8);
             if (ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, tp->prog.ng.p) && ngram_watch_allows(p, tp)) {
                 HIP_TRY(launch_ngram(op, a, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream, 2, u16.page, u16.sub));
@@ -801,9 +846,9 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
     if (v->char_width == 2 && u16.page < 0 && wide_filter_wanted(fp->prog.hdr.mode) && op != OP_MATCHES && !d_from && !d_end_state && !no_backward &&
         dict_env == 0 && v->row_stride * 2 < 8 * (uint64_t)kStripeBytes) {
         const DevProgram *tp = nullptr;
-        rc = get_program(p, which, 2, 10, &tp, nullptr);
+        rc = filter_route_wide(p, op, which, &tp);
         if (rc) return rc;
-        if (tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0)) {
+        if (tp) {
             const ScanArgs a = filter_scan_args(v, v->row_stride /* chars */, tp, op == OP_FIND ? p->t.fixed_len : -1, d_bitmap, d_start, d_end, d_packed, packed8);
             if (ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, tp->prog.ng.p) && ngram_watch_allows(p, tp)) {
                 HIP_TRY(launch_ngram(op, a, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream, 2, 0, 0));
@@ -833,22 +878,11 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
     // collapses on text that leaves the hot states (near-miss rows: 20 ms on the 10M-row batch), the filter's does not.
     if ((fp->prog.hdr.mode == MODE_HYBRID || fp->prog.hdr.mode == MODE_GLOBAL) && v->char_width == 1 && op != OP_MATCHES && !d_from && !d_end_state &&
         !no_backward && ngram_level() > 0 && dict_env == 0) {
-        const DevProgram *tp = nullptr;
-        rc = get_program(p, which, 1, 9, &tp, nullptr);
+        // (find() without bounded match lengths, no lengths form: the forward search automaton + backward walks for the starts, variant 12)
+        const DevProgram *tp = nullptr, *bwp = nullptr;
+        rc = filter_route_hbm(p, op, which, need_backward, true, &tp, &bwp);
         if (rc) return rc;
-        // find() without bounded match lengths (no lengths form): the forward search automaton + backward walks for the starts (variant 12)
-        static const bool unbounded_on = !(getenv("NEEDLE_PREFILTER_UNBOUNDED") && atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) == 0);
-        const DevProgram *bwp = nullptr;
-        if (!tp && op == OP_FIND && need_backward && unbounded_on) {
-            rc = get_program(p, which, 1, 12, &tp, nullptr);
-            if (rc) return rc;
-            if (tp) {
-                rc = get_program(p, W_BACKWARDS, 1, 1, &bwp, nullptr);
-                if (rc) return rc;
-                if (!bwp) tp = nullptr;
-            }
-        }
-        if (tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0 || bwp)) {
+        if (tp) {
             ScanArgs a = filter_scan_args(v, v->row_stride, tp, op == OP_FIND ? p->t.fixed_len : -1, d_bitmap, d_start, d_end, d_packed, packed8);
             if (bwp) a.bprog = bwp->d_blob, a.bhdr = bwp->prog.hdr;
             if (ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, tp->prog.ng.p) && ngram_watch_allows(p, tp)) {
@@ -1320,8 +1354,67 @@ static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_
     const bool need_backward = op == OP_FIND && p->t.fixed_len < 0;
     const DevProgram *fp = nullptr;
     int n_cus = 0;
+    // The n-gram candidate filter in front of packed rows (needle_ngram_packed.h): the filter program is chosen exactly as run_dev chooses it
+    // for the same pattern and char width (filter_route_*; the LDS programs' own filter below), under the same conditions -- containedIn(),
+    // or find() with a lengths form or a fixed length; no cursors -- with the same flood watch and the same needle_pattern_set_prefilter
+    // pin: it is the same program with the same counters.  No shape gate: the kernel is right for any amount of text.  find() of a pattern
+    // without bounded match lengths (variant 12) has no packed form.  NEEDLE_PREFILTER_PACKED=0: packed rows never take the filter (A/B).
+    static const bool pf_packed_on = !(getenv("NEEDLE_PREFILTER_PACKED") && atoi(getenv("NEEDLE_PREFILTER_PACKED")) == 0);
+    const bool filter_ok = pf_packed_on && op != OP_MATCHES && !d_from && ngram_level() > 0;
+    // launches tp's filter when its LDS footprint fits and the watch allows it; false: the call goes on to the next route / the plain kernel
+    auto try_filter = [&](const DevProgram *tp, int page, int sub, bool *launched) -> int {
+        *launched = false;
+        const uint32_t m = tp->prog.hdr.mode; // (the modes the packed filter kernel is instantiated for: the ones a filter is ever built on)
+        if (m != MODE_TABLE8 && m != MODE_TABLE16 && m != MODE_SPARSE && m != MODE_GLOBAL) return NEEDLE_OK;
+        if (op == OP_FIND && p->t.fixed_len > 65535) return NEEDLE_OK; // (the kernel's slot key holds a match length in 16 bits)
+        if (!ngram_packed_lds_bytes(tp->prog.hdr, tp->prog.ng.p) || !ngram_watch_allows(p, tp)) return NEEDLE_OK;
+        ScanArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.rows = (const uint8_t *)v->data;
+        sa.n_rows = v->n_rows;
+        sa.prog = tp->d_blob;
+        sa.hdr = tp->prog.hdr;
+        sa.fixed_len = op == OP_FIND ? p->t.fixed_len : -1;
+        sa.bitmap = d_bitmap;
+        sa.start = d_start;
+        sa.end = d_end;
+        sa.packed = op == OP_FIND ? d_packed : nullptr;
+        sa.packed8 = packed8 ? 1u : 0u;
+        HIP_TRY(launch_ngram_packed(op, sa, v->offsets, d_overflow, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream, cw, page, sub));
+        HIP_TRY(ngram_watch_after_launch(tp, (hipStream_t)stream));
+        *launched = true;
+        return NEEDLE_OK;
+    };
+    bool launched = false;
+    const Utf16Route u16 = cw == 2 ? utf16_route(p) : Utf16Route();
+    if (filter_ok && cw == 2 && u16.page >= 0) { // one-page UTF-16: the page's byte program, narrowed on load
+        const DevProgram *tp = nullptr;
+        filter_route_utf16_page(p, op, which, need_backward, u16, &tp, &n_cus);
+        if (tp) {
+            rc = try_filter(tp, u16.page, u16.sub, &launched);
+            if (rc || launched) return rc;
+        }
+    }
     rc = get_program(p, which, cw, need_backward ? 2 : 0, &fp, &n_cus);
     if (rc) return rc;
+    if (filter_ok && cw == 2 && u16.page < 0 && wide_filter_wanted(fp->prog.hdr.mode)) { // multi-page UTF-16: the WIDE filter
+        const DevProgram *tp = nullptr;
+        rc = filter_route_wide(p, op, which, &tp);
+        if (rc) return rc;
+        if (tp) {
+            rc = try_filter(tp, 0, 0, &launched);
+            if (rc || launched) return rc;
+        }
+    }
+    if (filter_ok && cw == 1 && (fp->prog.hdr.mode == MODE_HYBRID || fp->prog.hdr.mode == MODE_GLOBAL)) { // walks out of HBM / L2 (variant 9)
+        const DevProgram *tp = nullptr, *bwp = nullptr;
+        rc = filter_route_hbm(p, op, which, need_backward, false, &tp, &bwp);
+        if (rc) return rc;
+        if (tp) {
+            rc = try_filter(tp, 0, 0xFF, &launched);
+            if (rc || launched) return rc;
+        }
+    }
     bool lengths_form = false;
     if (need_backward && find_lengths_for(fp->prog.hdr.mode)) {
         const DevProgram *lp = nullptr;
@@ -1330,6 +1423,11 @@ static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_
         static const bool force_tables = getenv("NEEDLE_FIND_LENGTHS") && atoi(getenv("NEEDLE_FIND_LENGTHS")) > 1; // (as run_dev)
         if (lp && fp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR && !force_tables) lp = nullptr;
         if (lp) fp = lp, lengths_form = true;
+    }
+    // 8-bit rows of an LDS program that carries a filter of its own (fp->d_ng), as run_dev's last route
+    if (filter_ok && cw == 1 && fp->d_ng && fp->prog.ng.p.on && (op == OP_CONTAINED_IN || lengths_form || p->t.fixed_len >= 0)) {
+        rc = try_filter(fp, 0, 0xFF, &launched);
+        if (rc || launched) return rc;
     }
     PackedArgs a;
     memset(&a, 0, sizeof(a));

@@ -416,8 +416,9 @@ int needle_find_packed16_host(const needle_pattern *p, const needle_batch_view *
     return NEEDLE_OK;
 }
 
-// needle_find_host with start / end as ONE dword per row (low half start, high half end, 0xFFFF = no match: the form
-// needle_pack_start_len8_dev writes): 4 bytes per row over PCIe instead of 8.  Rows of at most 65 534 chars.
+// needle_find_host with start / end as ONE uint16 per row -- start | (end - start) << 8, 0xFFFF = no match, 0xFFFE = the match
+// (0, 256): pack8 of needle_device.h, stored by the scan kernel itself; NEEDLE_UNPACK8_START / _END decode it -- 2 bytes per row over
+// PCIe instead of 8.  Rows of at most 256 chars.
 int needle_find_packed8_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bitmap, uint16_t *start_len8) {
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
     int rc = check_host_view(v);

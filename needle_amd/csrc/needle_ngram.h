@@ -52,6 +52,8 @@ constexpr uint32_t kNgWaveLds = 2 * kNgQueue * 4 + 64 * 8; // (two queues: first
 // ... of its find-all form: the queue + per row of the group two slots for verified candidates (8 bytes each) and a counter
 constexpr uint32_t kNgRowSlots = 2;
 constexpr uint32_t kNgWaveLdsFA = kNgQueue * 4 + 64 * kNgRowSlots * 8 + 64 * 4;
+// ... of its packed-rows form (needle_ngram_packed.h): the two queues, the slots and the group's 65 row starts (64 rows + the end)
+constexpr uint32_t kNgWaveLdsPacked = kNgWaveLds + 272;
 constexpr uint32_t kNgWaves = 16;
 constexpr uint32_t kNgLdsCap = 160u * 1024u;
 

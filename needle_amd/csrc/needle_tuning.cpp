@@ -17,6 +17,8 @@ const Switch kSwitches[] = {
     {"NEEDLE_PREFILTER", "1", "layout", "n-gram candidate filter in front of the automaton (needle_ngram.hip): 0 never, 1 for automata in the compressed form, 2 for every LDS-table automaton that allows one"},
     {"NEEDLE_PREFILTER_LEVEL2", "1", "layout", "0: no second-level window (a candidate's 5-byte window looked up in a second bitmap before the automaton runs on it)"},
     {"NEEDLE_PREFILTER_UTF16", "1", "layout", "0: UTF-16 rows never take a filter kernel (patterns on one page of the BMP: the byte program's, text narrowed as it is loaded; several pages: the wide filter)"},
+    {"NEEDLE_PACKED_DIRECT_ABOVE", "2147483647", "debug", "packed rows behind the n-gram filter (needle_ngram_packed.h): a 64-row group whose span has more chars than this is walked row by row inside the filter kernel instead of being filtered (the default is the limit of the kernel's 32-bit stream positions; lower values let tests reach that path; answers are the same)"},
+    {"NEEDLE_PREFILTER_PACKED", "1", "layout", "0: packed row batches (needle_*_packed_dev) never take the n-gram filter kernel (needle_ngram_packed.h): every packed call walks the plain packed kernel, as with needle_pattern_set_prefilter(OFF)"},
     {"NEEDLE_PREFILTER_WIDE", "1", "layout", "0: UTF-16 rows of patterns on several pages of the BMP never take the wide filter (windows of four 16-bit code units, needle_ngram.h ngram_piece16); NEEDLE_PREFILTER_UTF16=0 switches it off too"},
     {"NEEDLE_PREFILTER_UNBOUNDED", "1", "layout", "0: find() of patterns without bounded match lengths never runs behind the n-gram filter (whose verified candidates find their starts by backward walks)"},
     {"NEEDLE_PREFILTER_STRIDE", "4", "layout", "largest window stride the n-gram filter may choose (2: never 4 -- keeps the second-level window for patterns whose shortest match is 7 chars)"},

@@ -796,10 +796,14 @@ class Pattern:
         return self._run_packed_host("matches", data, offsets, stream, out)
 
     def contained_in_packed(self, data, offsets, stream=None, out=None):
+        """Bitmap words of containedIn() of every packed row.  Device tensors (needle_contained_in_packed_dev): patterns with an n-gram
+        candidate filter run behind it on packed rows too (set_prefilter / prefilter_state apply as to the fixed-stride calls)."""
         return self._run_packed_host("contained_in", data, offsets, stream, out)
 
     def find_packed(self, data, offsets, stream=None, out=None):
-        """(bitmap words, start, end) of every packed row; device tensors give device tensors (needle_find_packed_dev)."""
+        """(bitmap words, start, end) of every packed row; device tensors give device tensors (needle_find_packed_dev).  Patterns with an
+        n-gram candidate filter and bounded match lengths run behind it (needle_ngram_packed.h; set_prefilter / prefilter_state apply as to
+        the fixed-stride calls, PREFILTER_OFF = the plain packed kernel); rows of any length, exact int32 positions."""
         return self._run_packed_host("find", data, offsets, stream, out)
 
     def find_strings(self, strings):
@@ -866,13 +870,14 @@ class Pattern:
         """find() of every packed row as ONE dword, start | end << 16 (0xFFFFFFFF = no match; NEEDLE_PACK16_OVER = a match ending past
         65 534).  Device tensors: needle_find_packed16_packed_dev -> (bitmap words, int32[n], overflow int32[1]: 1 when some row
         escaped); out: optional caller-owned (bitmap, results, zeroed overflow) tensors.  Numpy arrays: needle_find_packed16_packed_host
-        (rows of at most 65 534 chars) -> (bitmap words, uint32[n]).  unpack16_packed() decodes."""
+        (rows of at most 65 534 chars) -> (bitmap words, uint32[n]).  unpack16_packed() decodes.  The device form takes the n-gram
+        candidate filter as find_packed does, with the same escapes and flag."""
         return self._find_compact_packed(16, data, offsets, stream, out)
 
     def find_packed8_packed(self, data, offsets, stream=None, out=None):
         """find() of every packed row as ONE uint16, pack8's form (start | (end - start) << 8, 0xFFFF = no match, 0xFFFE = (0, 256);
         NEEDLE_PACK8_OVER = a match ending past 256).  Results as find_packed16_packed (int16 / uint16); the host form takes rows of
-        at most 256 chars.  unpack8_packed() decodes."""
+        at most 256 chars.  unpack8_packed() decodes.  The device form takes the n-gram candidate filter as find_packed does."""
         return self._find_compact_packed(8, data, offsets, stream, out)
 
     @staticmethod
