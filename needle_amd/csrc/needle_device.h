@@ -142,6 +142,8 @@ struct ScanArgs {
                              // matched rows' text goes there for the backward walk instead of being re-read from memory
     uint32_t defer_max_live; // survivor pool (needle_kernels.hip): a group with at most this many unresolved rows after
                              // a 128-byte line hands them to its wave's pool and ends; 0 = off
+    uint32_t pack_skip;      // packed mode, matches() / containedIn() (needle_scan.h, the two-slot loop): != 0 = the lines of rows that
+                             // have their verdict are not fetched; 0 = every line of an unfinished group is (NEEDLE_PACK_SKIP=0)
 };
 
 // The packed-rows scan kernel (needle_packed.h): rows are code units [offsets[r], offsets[r + 1]) of `s.rows`.

@@ -84,6 +84,10 @@ hipError_t launch_scan(int op, int char_width, const ScanArgs &a_in, int n_cus, 
     static const int defer_env = getenv("NEEDLE_DEFER") ? atoi(getenv("NEEDLE_DEFER")) : 16;
     a.defer_max_live = 0;
     if (defer_env > 0 && defer_env <= 32 && !a.from && !a.end_state && a.n_rows < (1ull << 32)) a.defer_max_live = (uint32_t)defer_env;
+    // packed-mode matches() / containedIn(): rows that have their verdict stop fetching.  NEEDLE_PACK_SKIP=0: same kernel, same fetch
+    // order, every line fetched (A/B on one build)
+    static const int pack_skip = getenv("NEEDLE_PACK_SKIP") ? atoi(getenv("NEEDLE_PACK_SKIP")) : 1;
+    a.pack_skip = pack_skip != 0;
     // unguarded kernels assume every row fills a whole number of tiles
     const bool guard = a.lengths != nullptr || a.from != nullptr || a.row_len == 0 ||
                        ((uint64_t)a.row_len * char_width) % sh.chb != 0;

@@ -44,9 +44,13 @@ template <int OP, int CW, int MODE, bool GUARD, int CHB, bool LEN = false>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void scan_kernel(const ScanArgs a) {
     using G = Geom<CHB>;
     // The survivor pool is compiled into the kernels of the big-table automata (64-byte tiles: the shape the launcher
-    // picks when the table fills the LDS).  Packed mode has no use for it (its lanes cost the same dead or alive and its
-    // scans run at the HBM rate), and the 128-byte-tile kernels have no registers to spare (128 VGPRs at 16 waves).
+    // picks when the table fills the LDS).  Packed mode has no use for it (its lanes cost the same dead or alive), and
+    // the 128-byte-tile kernels have no registers to spare (128 VGPRs at 16 waves).
     constexpr bool POOL = MODE != MODE_PACK && CHB == 64;
+    // Packed mode's matches() / containedIn() run at the HBM rate, so the bytes they ask for are their only lever: a
+    // wave keeps TWO groups in rotation and requests a group's next line only after the walk that tells which of its
+    // rows still need it (the two-slot loop below); the lines of rows that have their verdict are never fetched.
+    constexpr bool TWO = MODE == MODE_PACK && OP != OP_FIND && CHB == 128;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -156,6 +160,37 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void scan_kernel(const ScanArg
 #pragma unroll
             for (int t = 0; t < NT; ++t) R[t][j] = load_row16<NT == 1>(base + t * CHB + j * load_step + ((j & 1) ? o_odd : o_even));
     };
+    // Two-slot loop (TWO): store the tile held in R to LDS and, with do_fetch, request chunk `chunk` of group grp for the
+    // rows of `rows` only.  The loads are buffer loads from a descriptor over the tile's start whose range check is the
+    // mask: a lane of a dropped row gets an offset at or beyond num_records, so its load is counted (vmcnt) like any
+    // other but asks the memory for nothing and returns zeros -- no branch around a load (which makes the compiler
+    // drain vmcnt(0)), and the kPieces lanes of a row share its bit: a 128-byte line is requested whole,
+    // once, by one `nt` load, or not at all.
+    // The zeros are staged and walked by rows that already have their verdict.  That is safe only because those rows'
+    // states are absorbing on EVERY column, OVER, PAD and PRE included (needle_lower.cpp): the sink's row is all sink
+    // (matches()), containedIn()'s accepting rows lead to themselves; a ragged row (GUARD) that ended inside an earlier
+    // line takes PAD -- the identity in both loops -- for every later char whatever the tile holds.
+    constexpr uint32_t kDropBit = 0x80000000u; // = num_records: real offsets (< 8 rows + a line) stay below it, see last_group
+    auto stage_and_fetch_rows = [&](bool do_fetch, uint64_t grp, uint32_t chunk, uint64_t rows) __attribute__((always_inline)) {
+        if (!do_fetch) {
+#pragma unroll
+            for (int j = 0; j < G::kInstrs; ++j) store_piece(tile, j, R[0][j]);
+            return;
+        }
+        const uint8_t *base = a.rows + (grp << 6) * a.stride_bytes + chunk * CHB;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)kDropBit, 0x00020000);
+        const uint64_t drop = ~rows >> row_in_instr; // bit 8 * j: the row this lane fetches in load j is dropped
+        const uint32_t drop_lo = (uint32_t)drop, drop_hi = (uint32_t)(drop >> 32);
+#pragma unroll
+        for (int j = 0; j < G::kInstrs; ++j) {
+            store_piece(tile, j, R[0][j]);
+            asm volatile("" ::: "memory"); // keep store j ahead of load j (else all loads hoist: two tiles live)
+            const uint32_t d = ((j < 4 ? drop_lo : drop_hi) << (31 - 8 * (j & 3))) & kDropBit;
+            R[0][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(d | ((j & 1) ? o_odd : o_even)), (int)(j * (uint32_t)load_step),
+                                                            NEEDLE_NT_LOADS ? 2 /* nt */ : 0);
+            asm volatile("" ::: "memory");
+        }
+    };
     // The last 64-row group may hold fewer than 64 rows and its last chunk may reach past the end of the buffer:
     // it is fetched with every clamp applied, by the one wave that owns it, outside the pipelined loop.
     auto fetch_clamped = [&](uint64_t grp, uint32_t chunk) __attribute__((always_inline)) {
@@ -203,6 +238,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void scan_kernel(const ScanArg
         const uint32_t max_len = GUARD ? wave_max(len) : a.row_len;
         n_chunks = (max_len * CW + CHB - 1) / CHB;
         if (n_chunks == 0) n_chunks = 1; // empty rows still take one (fully PAD-guarded) step
+        if (TWO && GUARD) n_chunks = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_chunks); // (wave-uniform: the slots keep it in SGPRs)
         st = start_state;
         if (GUARD && OP == OP_FIND && a.from) {
             cursor = row_ok ? a.from[my_row] : -1;
@@ -463,7 +499,62 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void scan_kernel(const ScanArg
         p_ck = in_pool ? p_ck + NT : 0u; // (only rows in the pool advance)
     };
 
-    if (g < last_group) {
+    if constexpr (TWO) {
+        // ---- two groups in rotation.  Slot "cur" (g, ck, st, len, n_chunks) is the group whose tile R holds; slot "oth"
+        // (the *_o copies) names the NEXT tile its group needs -- chunk ck_o for the rows of live_o, all of them for a
+        // fresh group.  A step stages cur's tile, requests oth's, walks cur's -- so a line is asked for only after the
+        // walk that decides whether its row needs it, and one tile of loads is in flight per wave as in the one-group
+        // loop -- then advances cur (next chunk, or verdicts out and the wave's next group) and swaps the slots:
+        //   R = (A,0) | stage (A,0), request (B,0),            walk (A,0) -> liveA
+        //             | stage (B,0), request (A,1) for liveA,  walk (B,0) -> liveB
+        //             | stage (A,1), request (B,1) for liveB,  walk (A,1): A done, A := next group ...
+        // A wave down to one group (oth past last_group: its last groups, or fewer groups than two per wave) prefetches
+        // that group's next line whole, as the one-group loop does.
+        // (the offsets of the masked loads -- 8 rows + a line per lane, 56 rows in the scalar offset -- stay below kDropBit
+        // for rows up to 16 MiB; longer ones, which only NEEDLE_LONG_ROWS=0 brings here, take the clamped loop below)
+        if (a.stride_bytes > (1u << 24)) last_group = 0;
+        if (g < last_group) {
+            const uint64_t keep = a.pack_skip ? 0ull : ~0ull; // NEEDLE_PACK_SKIP=0: the new order, every line fetched
+            uint64_t g_o = g + wave_cnt, next_g = g + 2 * wave_cnt, live_o = ~0ull;
+            uint32_t ck = 0, ck_o = 0, st_o = start_state, len_o = 0, nch_o = 1;
+            if (g_o < last_group) {
+                begin_group(g_o);
+                st_o = st, len_o = len, nch_o = n_chunks;
+            }
+            begin_group(g);
+            fetch(g, 0);
+            for (;;) {
+                const bool two = g_o < last_group;
+                const bool pf_same = !two && ck + 1 < n_chunks;
+                stage_and_fetch_rows(two || pf_same, two ? g_o : g, two ? ck_o : ck + 1, two ? (live_o | keep) : ~0ull);
+                asm volatile("" ::: "memory"); // keep the request issued ahead of the walk
+                const uint64_t live = walk_tile(ck * (CHB / CW), ck * G::kPieces);
+                const bool group_done = live == 0ull || ck + 1 >= n_chunks;
+                if (group_done) {
+                    my_row = (g << 6) + lane; // (every group of this loop is whole)
+                    row_ok = true;
+                    finish_rows(g, std::false_type{});
+                    g = next_g;
+                    next_g += wave_cnt;
+                    ck = 0;
+                    if (g < last_group) begin_group(g);
+                } else {
+                    ++ck;
+                }
+                if (two) { // R holds oth's tile: it becomes cur
+                    const uint64_t tg = g; g = g_o; g_o = tg;
+                    const uint32_t tc = ck; ck = ck_o; ck_o = tc;
+                    const uint32_t ts = st; st = st_o; st_o = ts;
+                    const uint32_t tl = len; len = len_o; len_o = tl;
+                    const uint32_t tn = n_chunks; n_chunks = nch_o; nch_o = tn;
+                    live_o = group_done ? ~0ull : live;
+                } else if (g >= last_group) {
+                    break;
+                }
+            }
+            g = g < g_o ? g : g_o; // the wave's first group past the pipelined range
+        }
+    } else if (g < last_group) {
         uint32_t ck = 0;
         uint32_t pred_exit = 0xFFFFFFFFu; // chunk after which the previous group left early (prefetch predictor)
         begin_group(g);

@@ -44,6 +44,7 @@ const Switch kSwitches[] = {
     {"NEEDLE_MAX_PROG_LDS", "(device limit)", "size", "LDS bytes an automaton may take (tests lower it to force the HBM-table mode)"},
     {"NEEDLE_SHAPE", "(by LDS footprint)", "layout", "\"<waves>x<tile bytes>\" workgroup shape of the tiled scan kernel"},
     {"NEEDLE_PACK_WAVES", "14", "layout", "fewest waves a packed-mode workgroup may have before 128-byte tiles are given up"},
+    {"NEEDLE_PACK_SKIP", "1", "layout", "0: packed-mode matches() / containedIn() fetch every 128-byte line of every row of an unfinished 64-row group instead of only the lines of rows still without a verdict (same kernel and fetch order; for A/B runs)"},
     {"NEEDLE_SHORT_ROWS", "1", "layout", "0: rows of at most 64 bytes take the tiled kernel instead of the register-resident one"},
     {"NEEDLE_SHORT_WGS", "2", "layout", "workgroups per CU of the short-row kernel"},
     {"NEEDLE_DEFER", "16", "layout", "survivor pool: a 64-row group with at most this many unresolved rows hands them to the wave's pool (0: off; at most 32)"},

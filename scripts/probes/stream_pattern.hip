@@ -8,6 +8,9 @@
 //   3  wave-major: a wave owns one long contiguous range of the buffer (4096 streams spread over all of it)
 //   4  like 0, the waves of a CU rotated: wave w starts its chunk at unit (5 w) mod units and wraps
 //   5  like 0, but a wave takes its NEXT chunk from a global counter (atomicAdd) when it starts one: XCDs / CUs that get more bandwidth take more chunks
+//   6  scan-like (2) through buffer loads (the whole buffer behind one descriptor, the lane's 32-bit offset into it), every line fetched
+//   7  like 6 with a seeded 25 % of the rows' SECOND lines left out: their lanes' offsets lie beyond num_records, so the loads issue but ask
+//      for nothing (the packed-mode scan's two-slot loop, needle_scan.h).  Two rates: the bytes asked for, and the whole batch ("algorithmic")
 // hipcc --offload-arch=gfx950 -O3 -o /tmp/stream_pattern scripts/probes/stream_pattern.hip && /tmp/stream_pattern
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +18,13 @@
 #include <vector>
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__host__ __device__ inline bool skip_row(uint32_t row) { // lowbias32 of the row, one in four
+    uint32_t x = row + 0x5EED1234u;
+    x = (x ^ (x >> 16)) * 0x7FEB352Du;
+    x = (x ^ (x >> 15)) * 0x846CA68Bu;
+    return ((x ^ (x >> 16)) & 3u) == 0u;
+}
 
 template <int PF, int MODE>
 __global__ __launch_bounds__(1024) void stream_kernel(const uint8_t *base, uint64_t total, uint32_t chunk, uint32_t stride, uint32_t *sink) {
@@ -41,7 +51,7 @@ __global__ __launch_bounds__(1024) void stream_kernel(const uint8_t *base, uint6
             c = gw + i * n_waves;
         }
         if (c >= n_chunks) return base + (uint64_t)lane * 16u;
-        if (MODE == 2) { // units: line-major, 8 loads of 8 rows each per 128-byte line
+        if (MODE == 2 || MODE >= 6) { // units: line-major, 8 loads of 8 rows each per 128-byte line
             const uint32_t j = (uint32_t)u & 7u, line = (uint32_t)u >> 3;
             return base + c * chunk + (uint64_t)((lane >> 3) + 8u * j) * stride + line * 128u + (lane & 7u) * 16u;
         }
@@ -52,15 +62,27 @@ __global__ __launch_bounds__(1024) void stream_kernel(const uint8_t *base, uint6
     if (MODE == 3) my_units = per * units;
     else if (MODE == 1) my_units = ((n_chunks / 16 + gridDim.x - 1) / gridDim.x) * units;
     else my_units = ((n_chunks + n_waves - 1) / n_waves) * units;
+    // patterns 6 / 7: the same addresses as offsets into ONE buffer descriptor (the batch is < 4 GiB); a dropped row's lanes point beyond it
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(uint32_t)(total + 65536u), 0x00020000);
+    auto load = [&](uint64_t t) -> u32x4 {
+        const uint8_t *p = addr(t);
+        if (MODE < 6) return *(const u32x4 *)p;
+        uint32_t off = (uint32_t)(p - base);
+        if (MODE == 7 && ((t & (units - 1u)) >> 3) == 1u) { // a second line: dropped for a seeded quarter of the rows
+            const uint32_t row = off >> (31u - (uint32_t)__builtin_clz(stride)); // (the probe's strides are powers of two)
+            if (skip_row(row)) off = 0xF0000000u;
+        }
+        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, 0);
+    };
     u32x4 R[PF];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) R[k] = *(const u32x4 *)addr((uint64_t)k);
+    for (int k = 0; k < PF; ++k) R[k] = load((uint64_t)k);
     for (uint64_t t = 0; t < my_units; t += PF) {
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
             const u32x4 v = R[k];
             asm volatile("" ::: "memory");
-            R[k] = *(const u32x4 *)addr(t + PF + k);
+            R[k] = load(t + PF + k);
             acc ^= v[0] ^ v[1] ^ v[2] ^ v[3];
         }
     }
@@ -192,6 +214,15 @@ static void run(const char *name, const uint8_t *d, uint64_t total, uint32_t chu
         if (rep && ms < best) best = ms;
     }
     hipError_t e = hipGetLastError();
+    if (MODE == 7) { // the bytes asked for: every first line, the second lines of the rows kept
+        uint64_t kept = 0;
+        const uint64_t n_rows = total / stride;
+        for (uint64_t r = 0; r < n_rows; ++r) kept += skip_row((uint32_t)r) ? 1 : 2;
+        const double asked = (double)kept * 128.0;
+        printf("%-16s PF %d chunk %6u LDS %6zu: %.3f ms = %.2f TB/s asked for (%.4f of the lines), %.2f TB/s algorithmic%s\n", name, PF, chunk, lds, best,
+               asked / best * 1e-9, asked / (double)total, (double)total / best * 1e-9, e == hipSuccess ? "" : " (ERROR)");
+        return;
+    }
     printf("%-16s PF %d chunk %6u LDS %6zu: %.3f ms = %.2f TB/s%s\n", name, PF, chunk, lds, best, (double)total / best * 1e-9, e == hipSuccess ? "" : " (ERROR)");
 }
 
@@ -316,6 +347,8 @@ int main() {
         run<8, 1>("cu-interleaved", d, total, 16384, 256, d_sink, lds);
         run<4, 2>("scan-like", d, total, 16384, 256, d_sink, lds);
         run<8, 2>("scan-like", d, total, 16384, 256, d_sink, lds);
+        run<8, 6>("scan-like buffer", d, total, 16384, 256, d_sink, lds);
+        run<8, 7>("scan-like skip25", d, total, 16384, 256, d_sink, lds);
         run<4, 3>("wave-major", d, total, 16384, 256, d_sink, lds);
         run<8, 3>("wave-major", d, total, 16384, 256, d_sink, lds);
         run<4, 4>("filter-rotated", d, total, 16384, 256, d_sink, lds);
