@@ -11,7 +11,7 @@ SOURCES = ["needle_scan_find1.hip", "needle_scan_find2.hip", "needle_scan_contai
            "needle_packed_find_all2.hip", "needle_kernels.hip",
            "needle_stripe.hip", "needle_find_all.hip", "needle_find_all_ls.hip", "needle_compact.hip", "needle_ngram.hip", "needle_ngram_packed_contained1.hip", "needle_ngram_packed_contained2.hip", "needle_ngram_packed_find1.hip",
            "needle_ngram_packed_find2.hip", "needle_ngram_host.cpp", "needle_api.cpp", "needle_tuning.cpp", "needle_multi.cpp", "needle_lower.cpp", "needle_regex.cpp"]
-HEADERS = ["needle_device.h", "needle_walk.h", "needle_scan.h", "needle_packed.h", "needle_packed_find_all.h", "needle_find_all.h", "needle_lower.h", "needle_regex.h", "needle_ngram.h", "needle_ngram_kernel.h", "needle_ngram_packed.h", "needle_ngram_host.h", "needle_unicode_tables.h", os.path.join("..", "..", "include", "needle_hip.h")]
+HEADERS = ["needle_device.h", "needle_launch.h", "needle_walk.h", "needle_scan.h", "needle_packed.h", "needle_packed_find_all.h", "needle_find_all.h", "needle_lower.h", "needle_regex.h", "needle_ngram.h", "needle_ngram_kernel.h", "needle_ngram_packed.h", "needle_ngram_host.h", "needle_unicode_tables.h", os.path.join("..", "..", "include", "needle_hip.h")]
 
 
 TUNING_LIB = os.path.join(HERE, "libneedle_hip_tuning.so")

@@ -15,49 +15,9 @@
 #include "../../include/needle_hip.h"
 #include "needle_device.h"
 #include "needle_find_all.h"
+#include "needle_launch.h"
 #include "needle_lower.h"
 #include "needle_regex.h"
-
-namespace needle {
-hipError_t launch_scan(int op, int char_width, const ScanArgs &a, int n_cus, hipStream_t stream);
-hipError_t launch_packed(int op, int char_width, const PackedArgs &a, int n_cus, hipStream_t stream); // needle_packed_find2.hip
-hipError_t launch_packed_find_all(int char_width, const PackedFindAllArgs &a, int n_cus, hipStream_t stream); // needle_packed_find_all2.hip
-bool packed_find_all_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
-int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
-                      const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill); // needle_compact.hip
-bool shape_for_program(const ProgHeader &h, int char_width, int *waves, int *chb, int *tiles_in_f_rows);
-hipError_t launch_find_all(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream); // needle_find_all.hip
-hipError_t launch_find_all_lockstep(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream); // needle_find_all_ls.hip
-bool find_all_lockstep_shape_ok(const FindAllArgs &fa);
-hipError_t launch_find_all_collect(uint64_t n_rows, uint32_t slots, uint32_t k, const int32_t *s, const int32_t *e, int32_t *cursor,
-                                   uint32_t *counts, int32_t *starts, int32_t *ends, int32_t *any_hit, int n_cus, hipStream_t stream);
-hipError_t launch_long_rows(int char_width, const StripeArgs &a, int n_cus, hipStream_t stream);
-hipError_t launch_spec_len(const SpecArgs &a, hipStream_t stream);
-hipError_t launch_spec_init(const SpecArgs &a, hipStream_t stream);
-hipError_t launch_spec_fix(const SpecArgs &a, hipStream_t stream);
-hipError_t launch_spec_reduce(const SpecArgs &a, hipStream_t stream);
-hipError_t launch_backward_rows(int char_width, const StripeArgs &a, hipStream_t stream);
-#ifdef NEEDLE_TUNING // needle_dict.hip (two row sets per wave; measured, no faster -- DESIGN.md s4) is part of measurement builds only
-bool dict_kernel_applies(int char_width, const ScanArgs &a);
-hipError_t launch_dict(int op, const ScanArgs &a, int n_cus, hipStream_t stream);
-#endif
-// needle_ngram.hip: containedIn / find behind the n-gram candidate filter
-bool ngram_shape_ok(const ScanArgs &a);
-size_t ngram_lds_bytes(const ProgHeader &h, const NgramParams &ng);
-hipError_t launch_ngram(int op, const ScanArgs &a, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats, int n_cus, hipStream_t stream,
-                        int char_width = 1, int page = 0, int sub = 0xFF);
-size_t ngram_find_all_lds_bytes(const ProgHeader &h, const NgramParams &ng);
-hipError_t launch_ngram_find_all(const ScanArgs &a, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats, uint32_t slots, uint32_t *counts,
-                                 int32_t *starts, int32_t *ends, uint32_t *packed, int32_t *more, const uint64_t *offsets, bool count_only, int n_cus,
-                                 hipStream_t stream, int char_width, int page, int sub, uint32_t kshift);
-// needle_ngram_packed_find2.hip: the same filter in front of packed rows (needle_ngram_packed.h)
-size_t ngram_packed_lds_bytes(const ProgHeader &h, const NgramParams &ng);
-hipError_t launch_ngram_packed(int op, const ScanArgs &a, const uint64_t *offsets, int32_t *overflow, const NgramParams &ng, const uint32_t *d_bitmap,
-                               uint32_t *d_stats, int n_cus, hipStream_t stream, int char_width, int page, int sub);
-int ngram_level(); // needle_lower.cpp (NEEDLE_PREFILTER)
-hipError_t launch_unpack(const void *data, const uint64_t *offsets, uint64_t n_rows, uint32_t cw, void *out,
-                         uint64_t stride_bytes, uint32_t *lengths, int32_t *overflow, int n_cus, hipStream_t stream);
-} // namespace needle
 
 using namespace needle;
 
@@ -67,6 +27,13 @@ static int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
+
+#ifdef NEEDLE_TUNING // measurement builds only (scripts/build_tuning.sh): a switch that changes ANSWERS (start = end) never ships
+static bool debug_no_backward() {
+    static const bool on = getenv("NEEDLE_DEBUG_NO_BACKWARD") != nullptr;
+    return on;
+}
+#endif
 
 namespace needle {
 int set_error(int code, const std::string &msg) { return fail(code, msg); } // (needle_multi.cpp reports through the same channel)
@@ -166,24 +133,31 @@ struct DevProgram {
     }
 };
 
+// The forms a pattern's automaton is lowered to: the last part of a program's cache key (the numbers ARE the keys: they do not change).
+enum Variant : int {
+    V_PLAIN = 0,            // the ordinary program
+    V_WALK = 1,             // global-walk layout (backward automaton of find)
+    V_BACKMAPS = 2,         // forward + backward column maps
+    V_HBM_TABLE = 3,        // HBM-table layout forced (column maps + uint16 table in one blob: the speculative-stripe fix-up walks it)
+    V_FA_PLAIN = 4,         // 4 / 5 as 0 / 2 without the pair table (the one-pass find-all kernel)
+    V_FA_BACKMAPS = 5,
+    V_FA_LENGTHS = 6,       // the find-all "lengths" automaton (W_FORWARDS only; absent when the pattern does not allow it)
+    V_LENGTHS = 7,          // the same for find() in the scan kernels
+    V_FA_TRANSDUCER = 8,    // the find-all transducer (lock-step find-all, needle_find_all_ls.hip; absent when the pattern does not allow it)
+    V_FILTER_HBM = 9,       // the filter program of an automaton that fits the LDS in no form (lower_filter_hbm: HBM-table layout + n-gram filter;
+                            // W_CONTAINED_IN, or W_FORWARDS in the lengths form / for one-length patterns; absent when no filter can be built)
+    V_FILTER_WIDE = 10,     // the WIDE filter program (lower_filter_wide: char_width 2 only -- UTF-16 rows of a pattern on several pages of the BMP:
+                            // windows of four code units, UTF-16 HBM-table program); absent when no filter can be built
+    V_FA_RUNS = 11,         // the RUN transducer (lock-step find-all of patterns without bounded match lengths whose matches are runs: `[0-9]+`;
+                            // needle_lower.h lower_find_all_runs); absent when the pattern is not of that kind
+    V_FILTER_UNBOUNDED = 12 // V_FILTER_HBM for find() of a pattern WITHOUT bounded match lengths: the forward search automaton itself (no lengths
+                            // form) with the backward automaton's column maps in its LDS part -- verified candidates find their starts by backward walks
+};
+
 struct needle_pattern {
     RefTables t;
     std::mutex mu;
-    // (device, which, char_width, variant) -> program resident in that device's HBM
-    // variant: 0 plain, 1 global-walk layout (backward automaton of find), 2 forward + backward column maps,
-    //          3 HBM-table layout forced (column maps + uint16 table in one blob: the speculative-stripe fix-up walks it)
-    //          4 / 5 as 0 / 2 without the pair table (the one-pass find-all kernel)
-    //          6 the find-all "lengths" automaton (W_FORWARDS only; absent when the pattern does not allow it)
-    //          7 the same for find() in the scan kernels
-    //          8 the find-all transducer (lock-step find-all, needle_find_all_ls.hip; absent when the pattern does not allow it)
-    //          9 the filter program of an automaton that fits the LDS in no form (lower_filter_hbm: HBM-table layout + n-gram filter;
-    //            W_CONTAINED_IN, or W_FORWARDS in the lengths form / for one-length patterns; absent when no filter can be built)
-    //          12 variant 9 for find() of a pattern WITHOUT bounded match lengths: the forward search automaton itself (no lengths form) with
-    //            the backward automaton's column maps in its LDS part -- verified candidates find their starts by backward walks
-    //          11 the RUN transducer (lock-step find-all of patterns without bounded match lengths whose matches are runs: `[0-9]+`;
-    //            needle_lower.h lower_find_all_runs); absent when the pattern is not of that kind
-    //          10 the WIDE filter program (lower_filter_wide: char_width 2 only -- UTF-16 rows of a pattern on several pages of the BMP:
-    //            windows of four code units, UTF-16 HBM-table program); absent when no filter can be built
+    // (device, which, char_width, Variant) -> program resident in that device's HBM
     std::map<std::tuple<int, int, int, int>, DevProgram> cache;
     std::map<int, int> cus; // device -> CU count
     // needle_pattern_prefilter_info answers (lowering a big dictionary takes seconds): per `which`, filled once
@@ -240,13 +214,13 @@ static const MatchLengths *pattern_ml(const needle_pattern *cp) {
     return p->ml_state > 0 ? &p->ml : nullptr;
 }
 
-static int get_program(needle_pattern *p, int which, int cw, int variant, const DevProgram **out, int *n_cus) {
+static int get_program(needle_pattern *p, int which, int cw, Variant variant, const DevProgram **out, int *n_cus) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     // cw = 1 | page << 8: the BYTE program of the pattern rebased to one page of the BMP (UTF-16 rows narrowed on the fly: utf16_route)
     const int page = cw >> 8, cw_key = cw;
     cw &= 0xFF;
-    const bool wants_ml = variant == 6 || variant == 7 || variant == 8 || ((variant == 9 || variant == 10) && which == W_FORWARDS && p->t.fixed_len < 0);
+    const bool wants_ml = variant == V_FA_LENGTHS || variant == V_LENGTHS || variant == V_FA_TRANSDUCER || ((variant == V_FILTER_HBM || variant == V_FILTER_WIDE) && which == W_FORWARDS && p->t.fixed_len < 0);
     const MatchLengths *ml67 = wants_ml ? pattern_ml(p) : nullptr; // (before p->mu: see ml_mu)
     std::lock_guard<std::mutex> lk(p->mu);
     const RefTables *tt = &p->t;
@@ -275,44 +249,47 @@ static int get_program(needle_pattern *p, int which, int cw, int variant, const 
         p->cus[dev] = prop.multiProcessorCount;
     }
     if (n_cus) *n_cus = p->cus[dev];
-    auto key = std::make_tuple(dev, which, cw_key, variant);
+    auto key = std::make_tuple(dev, which, cw_key, (int)variant);
     auto it = p->cache.find(key);
     if (it == p->cache.end()) {
         DevProgram dp;
-        if (variant == 9 || variant == 10 || variant == 12) {
-            if ((wants_ml && !ml67) || (variant == 10 && cw != 2) || (variant == 12 && (which != W_FORWARDS || cw != 1))) {
+        if (variant == V_FILTER_HBM || variant == V_FILTER_WIDE || variant == V_FILTER_UNBOUNDED) {
+            if ((wants_ml && !ml67) || (variant == V_FILTER_WIDE && cw != 2) || (variant == V_FILTER_UNBOUNDED && (which != W_FORWARDS || cw != 1))) {
                 *out = nullptr;
                 return NEEDLE_OK;
             }
-            dp.prog = variant == 10 ? lower_filter_wide(*tt, (Which)which, ml67) : lower_filter_hbm(*tt, (Which)which, variant == 12 ? nullptr : ml67, variant == 12);
+            dp.prog = variant == V_FILTER_WIDE ? lower_filter_wide(*tt, (Which)which, ml67)
+                                               : lower_filter_hbm(*tt, (Which)which, variant == V_FILTER_UNBOUNDED ? nullptr : ml67, variant == V_FILTER_UNBOUNDED);
             if (dp.prog.blob.empty() || !dp.prog.ng.p.on) { // (no filter: the ordinary program is what runs)
                 p->cache.emplace(key, DevProgram());
                 *out = nullptr;
                 return NEEDLE_OK;
             }
-        } else if (variant == 11) { // the RUN transducer (lock-step find-all of `[0-9]+`-like patterns: lower_find_all_runs); absent when the pattern is not one
+        } else if (variant == V_FA_RUNS) { // (absent when the pattern is not one of runs)
             dp.prog = lower_find_all_runs(*tt, cw, max_prog_lds());
             if (dp.prog.blob.empty()) {
                 p->cache.emplace(key, DevProgram());
                 *out = nullptr;
                 return NEEDLE_OK;
             }
-        } else if (variant == 6 || variant == 7 || variant == 8) { // "lengths" form: the refined forward automaton + pend[] (needle_lower.h);
-                                            // 6: the find-all kernel's plain layout, 7: the scan kernels' (window addressing);
-                                            // 8: the find-all transducer built on it
+        } else if (variant == V_FA_LENGTHS || variant == V_LENGTHS || variant == V_FA_TRANSDUCER) {
+            // "lengths" form: the refined forward automaton + pend[] (needle_lower.h); V_FA_LENGTHS: the find-all kernel's plain layout,
+            // V_LENGTHS: the scan kernels' (window addressing); V_FA_TRANSDUCER: the find-all transducer built on it
             if (!ml67) {
                 *out = nullptr;
                 return NEEDLE_OK;
             }
-            dp.prog = variant == 8 ? lower_find_all_transducer(*tt, *ml67, cw, max_prog_lds())
-                                   : lower_match_lengths(*tt, *ml67, cw, max_prog_lds(), variant == 6);
+            dp.prog = variant == V_FA_TRANSDUCER ? lower_find_all_transducer(*tt, *ml67, cw, max_prog_lds())
+                                                 : lower_match_lengths(*tt, *ml67, cw, max_prog_lds(), variant == V_FA_LENGTHS);
             if (dp.prog.blob.empty()) { // (does not fit the LDS as a plain table: the ordinary program with backward walks)
                 p->cache.emplace(key, DevProgram());
                 *out = nullptr;
                 return NEEDLE_OK;
             }
-        } else
-        dp.prog = lower(*tt, (Which)which, cw, variant == 3 ? 0 : max_prog_lds(), variant == 1, variant == 2 || variant == 5, variant >= 4);
+        } else {
+            dp.prog = lower(*tt, (Which)which, cw, variant == V_HBM_TABLE ? 0 : max_prog_lds(), variant == V_WALK, variant == V_BACKMAPS || variant == V_FA_BACKMAPS,
+                            variant == V_FA_PLAIN || variant == V_FA_BACKMAPS);
+        }
         HIP_TRY(hipMalloc((void **)&dp.d_blob, dp.prog.blob.size()));
         if (hipError_t ce = hipMemcpy(dp.d_blob, dp.prog.blob.data(), dp.prog.blob.size(), hipMemcpyHostToDevice); ce != hipSuccess) {
             (void)hipFree(dp.d_blob);
@@ -341,7 +318,7 @@ static int get_program(needle_pattern *p, int which, int cw, int variant, const 
         }
         it = p->cache.emplace(key, std::move(dp)).first;
     }
-    *out = it->second.d_blob ? &it->second : nullptr; // (variant 6: an empty entry = "not available for this pattern / width")
+    *out = it->second.d_blob ? &it->second : nullptr; // (an empty entry = "not available for this pattern / width")
     return NEEDLE_OK;
 }
 
@@ -375,16 +352,85 @@ static bool offsets16_ok(const needle_batch_view *v, uint32_t limit) {
     return v->lengths ? v->row_stride <= 65536u : v->row_len <= limit;
 }
 
+// Where a scan's results go.  packed (find() only): a row's start / end as one dword -- or one uint16, with packed8 -- stored by the kernel
+// itself; start / end are not used then.
+struct ScanOut {
+    uint64_t *bitmap = nullptr;
+    int32_t *start = nullptr, *end = nullptr;
+    uint32_t *packed = nullptr;
+    bool packed8 = false;
+};
+
+// THE ScanArgs of forward program fp on n_rows rows at `rows`: bp = the backward program, where find() walks back for its starts
+// (nullptr: none), fixed_len = -1 or the pattern's one match length.  Every field not named here stays zero; a call that has more
+// to say (cursors, end states) adds it to what it gets back.  This is all a packed batch needs: its offsets travel beside the ScanArgs.
+static ScanArgs scan_args(const void *rows, uint64_t n_rows, const DevProgram *fp, const DevProgram *bp, int32_t fixed_len, const ScanOut &out) {
+    ScanArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = (const uint8_t *)rows;
+    a.n_rows = n_rows;
+    a.prog = fp->d_blob;
+    a.hdr = fp->prog.hdr;
+    if (bp) a.bprog = bp->d_blob, a.bhdr = bp->prog.hdr;
+    a.fixed_len = fixed_len;
+    a.bitmap = out.bitmap;
+    a.start = out.start;
+    a.end = out.end;
+    a.packed = out.packed;
+    a.packed8 = out.packed8 ? 1u : 0u;
+    return a;
+}
+static ScanArgs scan_args(const needle_packed_view *v, const DevProgram *fp, const DevProgram *bp, int32_t fixed_len, const ScanOut &out) {
+    return scan_args(v->data, v->n_rows, fp, bp, fixed_len, out);
+}
+// Fixed-stride rows.  stride: bytes between rows -- or CHARS, for UTF-16 rows behind a byte program's filter (launch_ngram and
+// launch_ngram_find_all with char_width 2 scale the addresses).
+static ScanArgs scan_args(const needle_batch_view *v, uint64_t stride, const DevProgram *fp, const DevProgram *bp, int32_t fixed_len, const ScanOut &out) {
+    ScanArgs a = scan_args(v->rows, v->n_rows, fp, bp, fixed_len, out);
+    a.stride_bytes = stride;
+    a.total_bytes = a.n_rows * a.stride_bytes;
+    a.row_len = v->row_len;
+    a.lengths = v->lengths;
+    return a;
+}
+
+static int which_of(int op) { return op == OP_MATCHES ? W_MATCHES : op == OP_CONTAINED_IN ? W_CONTAINED_IN : W_FORWARDS; }
+
+// The backward automaton find() walks for a match's start (global-walk layout) where the pattern has no one length and the forward
+// program is not the lengths form.
+static int backward_program(needle_pattern *p, int cw, const DevProgram **bp) { return get_program(p, W_BACKWARDS, cw, V_WALK, bp, nullptr); }
+
+// find()'s starts after the fact, one lane per matched row: indexBackwards from the lastMatch in d_end (needle_stripe.hip backward_rows).
+static hipError_t launch_find_starts(int cw, const void *rows, uint64_t n_rows, uint64_t stride_bytes, const DevProgram *fp, const DevProgram *bp, int32_t fixed_len,
+                                     uint64_t *d_bitmap, int32_t *d_start, int32_t *d_end, hipStream_t stream) {
+    StripeArgs ba;
+    memset(&ba, 0, sizeof(ba));
+    ba.rows = (const uint8_t *)rows;
+    ba.n_rows = n_rows;
+    ba.stride_bytes = stride_bytes;
+    ba.prog = fp->d_blob;
+    ba.hdr = fp->prog.hdr;
+    ba.bitmap = d_bitmap;
+    ba.start = d_start;
+    ba.end = d_end;
+    ba.fixed_len = fixed_len;
+    ba.op = OP_FIND;
+    if (bp) ba.bprog = bp->d_blob, ba.bhdr = bp->prog.hdr;
+    return launch_backward_rows(cw, ba, stream);
+}
+
 // Few, long rows: one row per lane would leave the chip idle.  Packed-mode automata take the stripe path (function
 // composition across 4 KiB stripes, needle_stripe.hip); NEEDLE_LONG_ROWS=0 turns it off, =1 forces it (tests).
-static bool wants_stripe_path(const needle_batch_view *v, const ProgHeader &hdr, bool has_cursors) {
+static int long_rows_force() {
     static const int force = getenv("NEEDLE_LONG_ROWS") ? atoi(getenv("NEEDLE_LONG_ROWS")) : -1;
+    return force;
+}
+static bool wants_stripe_path(const needle_batch_view *v, const ProgHeader &hdr, bool has_cursors) {
+    const int force = long_rows_force();
     const uint64_t stride_bytes = v->row_stride * v->char_width;
     const bool wanted = force >= 0 ? force == 1 : (v->n_rows < 65536 && stride_bytes >= 8 * (uint64_t)kStripeBytes);
     return wanted && hdr.mode == MODE_PACK && !has_cursors;
 }
-
-static int get_program(needle_pattern *p, int which, int cw, int variant, const DevProgram **out, int *n_cus);
 
 static int run_stripe_path(needle_pattern *p, int op, const needle_batch_view *v, const DevProgram *fp, int n_cus,
                            uint64_t *d_bitmap, int32_t *d_start, int32_t *d_end, void *stream) {
@@ -402,21 +448,18 @@ static int run_stripe_path(needle_pattern *p, int op, const needle_batch_view *v
     sa.bitmap = d_bitmap;
     sa.start = d_start;
     sa.end = d_end;
-    sa.fixed_len = -1;
+    sa.fixed_len = op == OP_FIND ? p->t.fixed_len : -1;
     sa.op = (uint32_t)op;
-    if (op == OP_FIND) {
-        sa.fixed_len = p->t.fixed_len;
-        if (sa.fixed_len < 0) {
-            const DevProgram *bp = nullptr;
-            int rc = get_program(p, W_BACKWARDS, (int)v->char_width, 1, &bp, nullptr);
-            if (rc) return rc;
-            sa.bprog = bp->d_blob;
-            sa.bhdr = bp->prog.hdr;
-        }
+    if (op == OP_FIND && sa.fixed_len < 0) {
+        const DevProgram *bp = nullptr;
+        int rc = backward_program(p, (int)v->char_width, &bp);
+        if (rc) return rc;
+        sa.bprog = bp->d_blob;
+        sa.bhdr = bp->prog.hdr;
     }
     // find(): pass 1 also marks the stripes that pass through an accepting state, and only the last such stripe of a row is walked
     // again for lastMatch (needle_stripe.hip).  NEEDLE_STRIPE_CAND=0: every stripe is (A/B, tests).
-    static const bool cand_on = !(getenv("NEEDLE_STRIPE_CAND") && atoi(getenv("NEEDLE_STRIPE_CAND")) == 0);
+    static const bool cand_on = (getenv("NEEDLE_STRIPE_CAND") ? atoi(getenv("NEEDLE_STRIPE_CAND")) : 1) != 0;
     const size_t fn_bytes = ((size_t)sa.n_rows * sa.spr * 4 + 15) & ~(size_t)15;
     const bool cand = op == OP_FIND && cand_on;
     HIP_TRY(scratch_malloc((void **)&sa.fn, fn_bytes * (cand ? 2 : 1) + (cand ? (size_t)sa.n_rows * 4 : 0), (hipStream_t)stream));
@@ -488,8 +531,12 @@ static hipError_t ngram_watch_after_launch(const DevProgram *fp, hipStream_t str
 struct Utf16Route {
     int page = -1, sub = 0;
 };
+static bool prefilter_utf16_off() {
+    static const bool off = (getenv("NEEDLE_PREFILTER_UTF16") ? atoi(getenv("NEEDLE_PREFILTER_UTF16")) : 1) == 0;
+    return off;
+}
 static Utf16Route utf16_route(const needle_pattern *cp) {
-    static const bool off = getenv("NEEDLE_PREFILTER_UTF16") && atoi(getenv("NEEDLE_PREFILTER_UTF16")) == 0;
+    const bool off = prefilter_utf16_off();
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     Utf16Route r;
     if (off) return r;
@@ -565,35 +612,55 @@ static Utf16Route utf16_route(const needle_pattern *cp) {
 
 // NEEDLE_FIND_LENGTHS: 0 = find() always by forward + backward walks, 1 (default) = the "lengths" automaton where the ordinary
 // program is a plain LDS table, 2 = also instead of the pair table (measured slower: DESIGN.md s4)
-static bool find_lengths_for(uint32_t mode) {
+static int find_lengths_level() {
     static const int level = getenv("NEEDLE_FIND_LENGTHS") ? atoi(getenv("NEEDLE_FIND_LENGTHS")) : 1;
-    static const bool sparse_too = !(getenv("NEEDLE_FIND_LENGTHS_SPARSE") && atoi(getenv("NEEDLE_FIND_LENGTHS_SPARSE")) == 0);
-    static const bool pair_too = !(getenv("NEEDLE_FIND_LENGTHS_PAIR") && atoi(getenv("NEEDLE_FIND_LENGTHS_PAIR")) == 0);
+    return level;
+}
+static bool find_lengths_for(uint32_t mode) {
+    static const bool sparse_too = (getenv("NEEDLE_FIND_LENGTHS_SPARSE") ? atoi(getenv("NEEDLE_FIND_LENGTHS_SPARSE")) : 1) != 0;
+    static const bool pair_too = (getenv("NEEDLE_FIND_LENGTHS_PAIR") ? atoi(getenv("NEEDLE_FIND_LENGTHS_PAIR")) : 1) != 0;
+    const int level = find_lengths_level();
     return level > 0 && (mode == MODE_TABLE8 || mode == MODE_TABLE16 || (sparse_too && mode == MODE_SPARSE) || ((pair_too || level > 1) && mode == MODE_PAIR));
 }
-
-static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v, uint64_t *d_bitmap, int32_t *d_start,
-                   int32_t *d_end, void *stream, const int32_t *d_from = nullptr, uint32_t *d_end_state = nullptr,
-                   bool no_backward = false, uint32_t *d_packed = nullptr, bool packed8 = false);
+// THE decision on find()'s lengths form -- the state the walk stops in remembers how long the match was, start = end - pend[state], no
+// indexBackwards, no text snapshots (needle_lower.h): given the mode of the ordinary program and the mode the lengths program came out in,
+// is the lengths program taken?  Where the ordinary program is a plain LDS table (the modes pend[] can be indexed in) -- but a pair-table
+// automaton whose lengths program no longer fits the pair table keeps its two walks: two chars per lookup beat the saved backward walk
+// (NEEDLE_FIND_LENGTHS=2 takes the plain table all the same).  NEEDLE_FIND_LENGTHS=0: never (A/B, tests).
+static bool takes_lengths_form(uint32_t ordinary_mode, uint32_t lengths_mode) {
+    const bool pair_lost = ordinary_mode == MODE_PAIR && lengths_mode != MODE_PAIR && find_lengths_level() <= 1;
+    return find_lengths_for(ordinary_mode) && !pair_lost;
+}
+// The lengths program find() takes in place of ordinary program fp on this device, or *lp_out = nullptr: it keeps fp and walks back.
+static int lengths_program(needle_pattern *p, int cw, const DevProgram *fp, const DevProgram **lp_out) {
+    *lp_out = nullptr;
+    if (!find_lengths_for(fp->prog.hdr.mode)) return NEEDLE_OK; // (not even lowered)
+    const DevProgram *lp = nullptr;
+    int rc = get_program(p, W_FORWARDS, cw, V_LENGTHS, &lp, nullptr);
+    if (rc) return rc;
+    if (lp && takes_lengths_form(fp->prog.hdr.mode, lp->prog.hdr.mode)) *lp_out = lp;
+    return NEEDLE_OK;
+}
 
 // The WIDE filter (lower_filter_wide) stands in for the UTF-16 scan kernels where the ordinary UTF-16 program is NOT a plain LDS table
 // (compressed automaton, hot rows + HBM table, HBM table): a latency-bound or collapsing walk.  NEEDLE_PREFILTER=2: for every
 // automaton that allows a filter (tests, A/B), as for 8-bit rows.  NEEDLE_PREFILTER_WIDE=0: never.
 static bool wide_filter_wanted(uint32_t ordinary_mode) {
     // (NEEDLE_PREFILTER_UTF16=0: no filter in front of UTF-16 rows at all -- the one-page route and this one)
-    static const bool off = (getenv("NEEDLE_PREFILTER_WIDE") && atoi(getenv("NEEDLE_PREFILTER_WIDE")) == 0) ||
-                            (getenv("NEEDLE_PREFILTER_UTF16") && atoi(getenv("NEEDLE_PREFILTER_UTF16")) == 0);
-    if (off || ngram_level() <= 0) return false;
+    static const bool wide_off = (getenv("NEEDLE_PREFILTER_WIDE") ? atoi(getenv("NEEDLE_PREFILTER_WIDE")) : 1) == 0;
+    if (wide_off || prefilter_utf16_off() || ngram_level() <= 0) return false;
     return ordinary_mode == MODE_SPARSE || ordinary_mode == MODE_HYBRID || ordinary_mode == MODE_GLOBAL || ngram_level() > 1;
 }
 
 // Few, long rows of an automaton too big for function composition: speculative stripes (needle_stripe.hip).  Returns
 // NEEDLE_OK with *done = false when the path does not apply or did not reach its fixpoint (the caller then walks the
-// rows one lane each).
+// rows one lane each).  scan_stripes(view, bitmap, start, end, end_state): the fixed-stride scan that runs pass 1 -- every stripe as a row
+// of its own, with its end state and without backward walks.
+template <class ScanStripes>
 static int run_speculative_stripes(needle_pattern *p, int op, const needle_batch_view *v, uint64_t *d_bitmap, int32_t *d_start,
-                                   int32_t *d_end, void *stream_, bool *done) {
+                                   int32_t *d_end, void *stream_, bool *done, ScanStripes &&scan_stripes) {
     *done = false;
-    static const int force = getenv("NEEDLE_LONG_ROWS") ? atoi(getenv("NEEDLE_LONG_ROWS")) : -1;
+    const int force = long_rows_force();
     const uint64_t stride_bytes = v->row_stride * v->char_width;
     // measured (scripts/mid_rows_table_rate.py): containedIn gains up to 60 000 rows; find breaks even around 20 000;
     // matches() usually dies in the first chars of a row, which only the lane path turns into an early exit
@@ -603,11 +670,11 @@ static int run_speculative_stripes(needle_pattern *p, int op, const needle_batch
     uint32_t stripe = kStripeBytes; // largest power of two <= 4 KiB that divides the row stride
     while (stripe > 256 && stride_bytes % stripe) stripe >>= 1;
     if (stride_bytes % stripe || stride_bytes / stripe < 2) return NEEDLE_OK;
-    const int which = op == OP_MATCHES ? W_MATCHES : op == OP_CONTAINED_IN ? W_CONTAINED_IN : W_FORWARDS;
+    const int which = which_of(op);
     if (op != OP_MATCHES && p->t.dfa[which].accepting[0]) return NEEDLE_OK; // an accepting start state makes every stripe start look like a match
     const DevProgram *gp = nullptr, *fp = nullptr, *bp = nullptr;
     int n_cus = 0;
-    int rc = get_program(p, which, (int)v->char_width, 3, &gp, &n_cus); // HBM-table layout: column maps + uint16 table
+    int rc = get_program(p, which, (int)v->char_width, V_HBM_TABLE, &gp, &n_cus); // column maps + uint16 table
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     SpecArgs sa;
@@ -656,7 +723,7 @@ static int run_speculative_stripes(needle_pattern *p, int op, const needle_batch
     sv.n_rows = ns;
     sv.row_stride = stripe / v->char_width;
     sv.lengths = sa.slen;
-    rc = run_dev(p, op, &sv, (uint64_t *)(tmp + o_bm), spec_start, spec_last, stream_, nullptr, spec_end_state, true);
+    rc = scan_stripes(&sv, (uint64_t *)(tmp + o_bm), spec_start, spec_last, spec_end_state);
     if (rc) return finish(rc);
     e = launch_spec_init(sa, stream);
     if (e != hipSuccess) return finish(hip_fail(e, "spec_init"));
@@ -676,59 +743,17 @@ static int run_speculative_stripes(needle_pattern *p, int op, const needle_batch
     e = launch_spec_reduce(sa, stream);
     if (e != hipSuccess) return finish(hip_fail(e, "spec_reduce"));
     if (op == OP_FIND) { // matched bits + start: indexBackwards from lastMatch, one lane per row
-        rc = get_program(p, W_FORWARDS, (int)v->char_width, p->t.fixed_len < 0 ? 2 : 0, &fp, nullptr);
+        rc = get_program(p, W_FORWARDS, (int)v->char_width, p->t.fixed_len < 0 ? V_BACKMAPS : V_PLAIN, &fp, nullptr);
         if (rc) return finish(rc);
-        StripeArgs ba;
-        memset(&ba, 0, sizeof(ba));
-        ba.rows = (const uint8_t *)v->rows;
-        ba.n_rows = v->n_rows;
-        ba.stride_bytes = stride_bytes;
-        ba.prog = fp->d_blob;
-        ba.hdr = fp->prog.hdr;
-        ba.bitmap = d_bitmap;
-        ba.start = d_start;
-        ba.end = d_end;
-        ba.fixed_len = p->t.fixed_len;
-        ba.op = OP_FIND;
-        if (ba.fixed_len < 0) {
-            rc = get_program(p, W_BACKWARDS, (int)v->char_width, 1, &bp, nullptr);
-            if (rc) return finish(rc);
-            ba.bprog = bp->d_blob;
-            ba.bhdr = bp->prog.hdr;
-        }
-        e = launch_backward_rows((int)v->char_width, ba, stream);
+        if (p->t.fixed_len < 0 && (rc = backward_program(p, (int)v->char_width, &bp))) return finish(rc);
+        e = launch_find_starts((int)v->char_width, v->rows, v->n_rows, stride_bytes, fp, bp, p->t.fixed_len, d_bitmap, d_start, d_end, stream);
         if (e != hipSuccess) return finish(hip_fail(e, "backward_rows"));
     }
     *done = true;
     return finish(NEEDLE_OK);
 }
 
-// Launch arguments of the filter kernel (needle_ngram.hip) for program `tp` on batch `v`.  stride: bytes between rows -- or CHARS, for UTF-16
-// rows behind the byte program (launch_ngram with char_width 2 scales the addresses).
-static ScanArgs filter_scan_args(const needle_batch_view *v, uint64_t stride, const DevProgram *tp, int32_t fixed_len, uint64_t *d_bitmap, int32_t *d_start,
-                                 int32_t *d_end, uint32_t *d_packed, bool packed8 = false) {
-    ScanArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rows = (const uint8_t *)v->rows;
-    a.n_rows = v->n_rows;
-    a.stride_bytes = stride;
-    a.total_bytes = a.n_rows * a.stride_bytes;
-    a.row_len = v->row_len;
-    a.lengths = v->lengths;
-    a.prog = tp->d_blob;
-    a.hdr = tp->prog.hdr;
-    a.fixed_len = fixed_len;
-    a.bitmap = d_bitmap;
-    a.start = d_start;
-    a.end = d_end;
-    a.packed = d_packed;
-    a.packed8 = packed8 ? 1u : 0u;
-    return a;
-}
-
-// ---- Which filter program serves (pattern, op, char width): ONE choice for fixed-stride rows (run_dev) and packed rows (run_packed_dev).
-// Each function answers for one route; *tp == nullptr: not this route.  The callers add what is theirs: the batch's shape, cursors, the
-// LDS footprint of their kernel, the flood watch.
+// ---- What each filter route picks.  *tp_out == nullptr: not this route.  The ORDER of the routes and their preconditions are choose_route's.
 // UTF-16 rows of a pattern on ONE page of the BMP: the byte program of that page, the text narrowed on load (utf16_route, narrow16).  Every
 // step is speculative -- lowering and uploading the page's byte programs for a pattern that may have no filter at all -- so a failure
 // means "route unavailable", never an error.
@@ -736,47 +761,52 @@ static void filter_route_utf16_page(needle_pattern *p, int op, int which, bool n
     *tp_out = nullptr;
     const DevProgram *tp = nullptr;
     const int cw8 = 1 | (u16.page << 8); // the byte program of the pattern's page
-    if (get_program(p, which, cw8, need_backward ? 2 : 0, &tp, n_cus)) return;
+    if (get_program(p, which, cw8, need_backward ? V_BACKMAPS : V_PLAIN, &tp, n_cus)) return;
     bool ok = false;
     if (tp->prog.hdr.mode == MODE_HYBRID || tp->prog.hdr.mode == MODE_GLOBAL) {
-        if (get_program(p, which, cw8, 9, &tp, nullptr)) return;
+        if (get_program(p, which, cw8, V_FILTER_HBM, &tp, nullptr)) return;
         ok = tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0);
     } else {
         bool lengths8 = false;
-        if (need_backward && find_lengths_for(tp->prog.hdr.mode)) {
+        if (need_backward) {
             const DevProgram *lp = nullptr;
-            if (get_program(p, W_FORWARDS, cw8, 7, &lp, nullptr)) return;
+            if (lengths_program(p, cw8, tp, &lp)) return;
+            // (this route never trades a pair table away, not even under NEEDLE_FIND_LENGTHS=2: such a program carries no filter anyway)
             if (lp && !(tp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR)) tp = lp, lengths8 = true;
         }
         ok = tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || lengths8 || p->t.fixed_len >= 0);
     }
     if (ok) *tp_out = tp;
 }
-// UTF-16 rows of a pattern on SEVERAL pages: the WIDE filter's program (variant 10), where wide_filter_wanted() says so for the ordinary
-// UTF-16 program's mode.
+// UTF-16 rows of a pattern on SEVERAL pages: the WIDE filter's program, where wide_filter_wanted() says so for the ordinary UTF-16
+// program's mode.
 static int filter_route_wide(needle_pattern *p, int op, int which, const DevProgram **tp_out) {
     *tp_out = nullptr;
     const DevProgram *tp = nullptr;
-    int rc = get_program(p, which, 2, 10, &tp, nullptr);
+    int rc = get_program(p, which, 2, V_FILTER_WIDE, &tp, nullptr);
     if (rc) return rc;
     if (tp && tp->d_ng && tp->prog.ng.p.on && (op == OP_CONTAINED_IN || tp->prog.hdr.fa_len_off || p->t.fixed_len >= 0)) *tp_out = tp;
     return NEEDLE_OK;
 }
+// NEEDLE_PREFILTER_UNBOUNDED=0: find() of a pattern without bounded match lengths never runs behind the filter.
+static bool prefilter_unbounded_on() {
+    static const bool on = (getenv("NEEDLE_PREFILTER_UNBOUNDED") ? atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) : 1) != 0;
+    return on;
+}
 // 8-bit rows of an automaton that fits the LDS in no form (hot rows + HBM table, or the HBM table alone): the filter with verify walks out
-// of HBM / L2 (variant 9).  allow_unbounded: find() without bounded match lengths may take the forward search automaton + backward walks
-// for the starts (variant 12, *bwp_out = the backward program; NEEDLE_PREFILTER_UNBOUNDED=0: never).
+// of HBM / L2 (V_FILTER_HBM).  allow_unbounded: find() without bounded match lengths may take the forward search automaton + backward walks
+// for the starts (V_FILTER_UNBOUNDED, *bwp_out = the backward program).
 static int filter_route_hbm(needle_pattern *p, int op, int which, bool need_backward, bool allow_unbounded, const DevProgram **tp_out, const DevProgram **bwp_out) {
     *tp_out = *bwp_out = nullptr;
     const DevProgram *tp = nullptr;
-    int rc = get_program(p, which, 1, 9, &tp, nullptr);
+    int rc = get_program(p, which, 1, V_FILTER_HBM, &tp, nullptr);
     if (rc) return rc;
-    static const bool unbounded_on = !(getenv("NEEDLE_PREFILTER_UNBOUNDED") && atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) == 0);
     const DevProgram *bwp = nullptr;
-    if (!tp && op == OP_FIND && need_backward && unbounded_on && allow_unbounded) {
-        rc = get_program(p, which, 1, 12, &tp, nullptr);
+    if (!tp && op == OP_FIND && need_backward && prefilter_unbounded_on() && allow_unbounded) {
+        rc = get_program(p, which, 1, V_FILTER_UNBOUNDED, &tp, nullptr);
         if (rc) return rc;
         if (tp) {
-            rc = get_program(p, W_BACKWARDS, 1, 1, &bwp, nullptr);
+            rc = backward_program(p, 1, &bwp);
             if (rc) return rc;
             if (!bwp) tp = nullptr;
         }
@@ -785,11 +815,121 @@ static int filter_route_hbm(needle_pattern *p, int op, int which, bool need_back
     return NEEDLE_OK;
 }
 
+// ---- THE route of a call: which program, and which kernel family, serves (pattern, op, char width, what the call carries) -- one
+// decision for fixed-stride rows (run_dev) and packed rows (run_packed_dev), so that a pattern takes the same program on both.
+struct Route {
+    enum Kind {
+        SCAN,   // the layout's plain scan kernel walks fp (+ bp)
+        FILTER, // the layout's n-gram filter kernel runs in front of fp (+ bp): launched by the time choose_route returns
+        DONE    // one of the layout's own paths (RouteCaps / own_paths) has served the call
+    } kind = SCAN;
+    const DevProgram *fp = nullptr; // the forward program
+    const DevProgram *bp = nullptr; // the backward program find() walks for its starts; nullptr: none needed
+    bool lengths_form = false;      // SCAN: fp is find()'s lengths program (start = end - pend[state])
+    bool own_filter = false;        // SCAN: fp carries a filter of its own that this call may take: the caller offers it to its filter tail first
+    int page = 0, sub = 0xFF;       // FILTER in front of UTF-16 rows: the page the byte program stands for and the byte of every char outside it
+    int n_cus = 0;
+};
+// What the layout, its kernels and the call's arguments allow.  The defaults leave every route open.
+struct RouteCaps {
+    bool filter = true;         // a filter kernel may serve the call at all
+    bool stand_in = true;       // ... with a program OTHER than the one the plain kernel would walk (routes 1, 3 and 4 below)
+    bool utf16 = true;          // the UTF-16 filter routes (1 and 3) are open
+    bool unbounded_find = true; // find() of a pattern without bounded match lengths may run behind the filter, its starts by backward walks
+    bool lengths_form = true;   // find() may take the lengths program
+};
+// The routes in their order -- the first that applies and that its layout's filter tail launches is the call's:
+//   1. UTF-16 rows, pattern on ONE page of the BMP: the filter of that page's byte program.  Tried BEFORE the ordinary UTF-16 program is asked
+//      for: a call it serves does not lower that program.
+//   2. the ordinary program of (op, char width): what the plain kernel walks, and what decides the routes below.
+//   3. UTF-16 rows, pattern on SEVERAL pages, wide_filter_wanted(ordinary mode): the WIDE filter program.
+//      -- own_paths(r, &done): the layout's own kernels, once the ordinary program is known (fixed stride: the stripe paths) --
+//   4. 8-bit rows, ordinary program a hot-rows / HBM-table one: the filter program with its walks out of HBM / L2.
+//   5. find() without one match length: the lengths program in place of the ordinary one (lengths_program), else the backward program.
+//   6. 8-bit rows, the program of 5 carries a filter of its own: Route::own_filter -- the caller's last filter launch, in front of its plain kernel.
+// try_filter(candidate, &launched) is the layout's filter tail: its kernel's gate, then the flood watch (which counts: asked LAST, once per
+// candidate that passed the gate), the launch, the stats copy.  launched == false: the order goes on.
+// No filter route at all for matches(), under NEEDLE_PREFILTER=0, or where caps.filter says no.  Where the two layouts DIFFER, on purpose:
+//   - fixed stride: per-row cursors, the speculative-stripe pass (d_end_state, no_backward) close every filter route, and that pass keeps the
+//     ordinary program (no lengths form); packed: cursors close the filter routes, NEEDLE_PREFILTER_PACKED=0 does too.
+//   - find() of a pattern without bounded match lengths behind a filter (V_FILTER_UNBOUNDED in route 4, backward walks in route 6) is fixed-stride
+//     only: the packed filter kernel has no backward walk.
+//   - the gates (inside try_filter): fixed stride asks ngram_shape_ok (stride 64 .. 4096 B, >= 16 KiB in all, ...) and ngram_lds_bytes; packed has no
+//     shape gate, but the four modes its kernel is instantiated for, fixed_len <= 65535 and ngram_packed_lds_bytes.
+//   - fixed stride closes routes 1 and 3 from a stride of 8 x kStripeBytes on (such rows are the stripe paths'); packed rows have no stride.
+//   - fixed stride, measurement builds: NEEDLE_DICT closes routes 1, 3 and 4 (caps.stand_in), not 6.
+template <class TryFilter, class OwnPaths>
+static int choose_route(needle_pattern *p, int op, int cw, const RouteCaps &caps, TryFilter &&try_filter, OwnPaths &&own_paths, Route *r) {
+    const int which = which_of(op);
+    const bool need_backward = op == OP_FIND && p->t.fixed_len < 0;
+    const bool filter = caps.filter && op != OP_MATCHES && ngram_level() > 0, stand_in = filter && caps.stand_in;
+    const Utf16Route u16 = cw == 2 ? utf16_route(p) : Utf16Route();
+    bool served = false;
+    auto offer = [&](const DevProgram *tp, const DevProgram *bwp, int page, int sub) {
+        Route c = *r;
+        c.kind = Route::FILTER, c.fp = tp, c.bp = bwp, c.page = page, c.sub = sub;
+        const int rc = try_filter(c, &served);
+        if (served) *r = c;
+        return rc;
+    };
+    int rc = NEEDLE_OK;
+    if (stand_in && cw == 2 && caps.utf16 && u16.page >= 0) { // 1
+        const DevProgram *tp = nullptr;
+        filter_route_utf16_page(p, op, which, need_backward, u16, &tp, &r->n_cus);
+        if (tp && ((rc = offer(tp, nullptr, u16.page, u16.sub)) || served)) return rc;
+    }
+    rc = get_program(p, which, cw, need_backward ? V_BACKMAPS : V_PLAIN, &r->fp, &r->n_cus); // 2
+    if (rc) return rc;
+    if (stand_in && cw == 2 && caps.utf16 && u16.page < 0 && wide_filter_wanted(r->fp->prog.hdr.mode)) { // 3
+        const DevProgram *tp = nullptr;
+        rc = filter_route_wide(p, op, which, &tp);
+        if (rc) return rc;
+        if (tp && ((rc = offer(tp, nullptr, 0, 0)) || served)) return rc;
+    }
+    rc = own_paths(r, &served);
+    if (served) r->kind = Route::DONE;
+    if (rc || served) return rc;
+    if (stand_in && cw == 1 && (r->fp->prog.hdr.mode == MODE_HYBRID || r->fp->prog.hdr.mode == MODE_GLOBAL)) { // 4
+        const DevProgram *tp = nullptr, *bwp = nullptr;
+        rc = filter_route_hbm(p, op, which, need_backward, caps.unbounded_find, &tp, &bwp);
+        if (rc) return rc;
+        if (tp && ((rc = offer(tp, bwp, 0, 0xFF)) || served)) return rc;
+    }
+    if (need_backward && caps.lengths_form) { // 5
+        const DevProgram *lp = nullptr;
+        rc = lengths_program(p, cw, r->fp, &lp);
+        if (rc) return rc;
+        if (lp) r->fp = lp, r->lengths_form = true;
+    }
+    if (need_backward && !r->lengths_form) {
+        rc = backward_program(p, cw, &r->bp);
+        if (rc) return rc;
+    }
+    // 6 (find() without bounded match lengths: verified candidates find their starts by indexBackwards, the lock-step backward walk on text out of L2)
+    const bool by_backward_walk = r->bp && caps.unbounded_find && prefilter_unbounded_on();
+    r->own_filter = filter && cw == 1 && r->fp->d_ng && r->fp->prog.ng.p.on && (op == OP_CONTAINED_IN || r->lengths_form || p->t.fixed_len >= 0 || by_backward_walk);
+    return NEEDLE_OK;
+}
+
+// THE tail of a fixed-stride filter launch (needle_ngram.hip) of program tp: the kernel's gate -- the batch's shape, the LDS footprint --, the
+// flood watch LAST (it counts what it allows), the launch, the stats copy behind it.  *launched == false: the call goes on to its next route.
+static int launch_filter(const needle_pattern *p, int op, const ScanArgs &a, const DevProgram *tp, int n_cus, hipStream_t stream, int cw, int page, int sub,
+                         bool *launched) {
+    *launched = false;
+    if (!ngram_shape_ok(a) || !ngram_lds_bytes(a.hdr, tp->prog.ng.p) || !ngram_watch_allows(p, tp)) return NEEDLE_OK;
+    HIP_TRY(launch_ngram(op, a, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, stream, cw, page, sub));
+    HIP_TRY(ngram_watch_after_launch(tp, stream));
+    *launched = true;
+    return NEEDLE_OK;
+}
+
 // d_packed (OP_FIND, needle_find_packed16_dev): a row's start / end go there as one dword, stored by the scan kernel itself;
 // d_start / d_end are not used.  The paths for few long rows (stripes) and the opt-in two-row-set kernel keep their int32
 // arrays: they run into scratch and one pack pass follows.
-static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v, uint64_t *d_bitmap, int32_t *d_start,
-                   int32_t *d_end, void *stream, const int32_t *d_from, uint32_t *d_end_state, bool no_backward, uint32_t *d_packed, bool packed8) {
+// d_end_state / no_backward: the speculative-stripe pass (every stripe's end state; only lastMatch is wanted).
+static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v, uint64_t *d_bitmap, int32_t *d_start, int32_t *d_end, void *stream_,
+                   const int32_t *d_from = nullptr, uint32_t *d_end_state = nullptr, bool no_backward = false, uint32_t *d_packed = nullptr,
+                   bool packed8 = false) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
     int rc = check_view(v, true);
@@ -797,146 +937,71 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!d_bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
     if (op == OP_FIND && !d_packed && (!d_start || !d_end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
 #ifdef NEEDLE_TUNING
     static const int dict_env = getenv("NEEDLE_DICT") ? atoi(getenv("NEEDLE_DICT")) : 0;
 #else
     constexpr int dict_env = 0;
 #endif
+    const int cw = (int)v->char_width;
+    const uint64_t stride_bytes = v->row_stride * v->char_width;
     // (NEEDLE_LONG_ROWS=1 forces the stripe paths for any stride: they only know the int32 arrays)
-    static const bool long_rows_forced = getenv("NEEDLE_LONG_ROWS") && atoi(getenv("NEEDLE_LONG_ROWS")) == 1;
-    if (d_packed && (dict_env > 0 || long_rows_forced || v->row_stride * v->char_width >= 8 * (uint64_t)kStripeBytes)) {
+    if (d_packed && (dict_env > 0 || long_rows_force() == 1 || stride_bytes >= 8 * (uint64_t)kStripeBytes)) {
         if (packed8) return fail(NEEDLE_ERR_UNSUPPORTED, "needle_find_packed8_dev: not on the stripe / two-row-set paths (tuning switches)");
         int32_t *tmp = nullptr;
-        HIP_TRY(scratch_malloc((void **)&tmp, (size_t)v->n_rows * 8, (hipStream_t)stream));
-        rc = run_dev(cp, op, v, d_bitmap, tmp, tmp + v->n_rows, stream, d_from, d_end_state, no_backward, nullptr);
-        if (rc == NEEDLE_OK) rc = needle_pack_start_end16_dev(tmp, tmp + v->n_rows, v->n_rows, d_packed, stream);
-        (void)scratch_free(tmp, (hipStream_t)stream);
+        HIP_TRY(scratch_malloc((void **)&tmp, (size_t)v->n_rows * 8, stream));
+        rc = run_dev(cp, op, v, d_bitmap, tmp, tmp + v->n_rows, stream_, d_from, d_end_state, no_backward, nullptr);
+        if (rc == NEEDLE_OK) rc = needle_pack_start_end16_dev(tmp, tmp + v->n_rows, v->n_rows, d_packed, stream_);
+        (void)scratch_free(tmp, stream);
         return rc;
     }
-
-    const int which = op == OP_MATCHES ? W_MATCHES : op == OP_CONTAINED_IN ? W_CONTAINED_IN : W_FORWARDS;
-    const DevProgram *fp = nullptr, *bp = nullptr;
-    int n_cus = 0;
-    const bool need_backward = op == OP_FIND && p->t.fixed_len < 0;
-    // UTF-16 rows (Java's strings) of a pattern that lives on one page of the BMP -- ASCII / Latin-1, Cyrillic, Greek ... dictionaries: behind
-    // the n-gram filter of the BYTE program of that page, the text narrowed as it is loaded (utf16_route above; needle_ngram.h narrow16).
-    // The program is chosen as for 8-bit rows below; whatever rules the filter out there (no filter for this automaton, the shape, the
-    // flood watch) leaves these rows to the UTF-16 kernels.
-    const Utf16Route u16 = v->char_width == 2 ? utf16_route(p) : Utf16Route();
-    if (v->char_width == 2 && op != OP_MATCHES && !d_from && !d_end_state && !no_backward && ngram_level() > 0 && dict_env == 0 && u16.page >= 0 &&
-        v->row_stride * 2 < 8 * (uint64_t)kStripeBytes) do {
-        // (a failure inside this route means "route unavailable", the UTF-16 kernels below serve the call)
-        const DevProgram *tp = nullptr;
-        filter_route_utf16_page(p, op, which, need_backward, u16, &tp, &n_cus);
-        if (tp) {
-            const ScanArgs a = filter_scan_args(v, v->row_stride /* chars */, tp, op == OP_FIND ? p->t.fixed_len : -1, d_bitmap, d_start, d_end, d_packed, packed8);
-            if (ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, tp->prog.ng.p) && ngram_watch_allows(p, tp)) {
-                HIP_TRY(launch_ngram(op, a, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream, 2, u16.page, u16.sub));
-                HIP_TRY(ngram_watch_after_launch(tp, (hipStream_t)stream));
-                return NEEDLE_OK;
-            }
-        }
-    } while (0);
-    rc = get_program(p, which, (int)v->char_width, need_backward ? 2 : 0, &fp, &n_cus);
-    if (rc) return rc;
-    // UTF-16 rows of a pattern that lives on SEVERAL pages of the BMP (Latin + Cyrillic + CJK dictionaries: DFA.java:438-463, the reference's
-    // class map covers every code unit of any pattern) and whose automaton is too big for a plain LDS table: the WIDE filter -- windows of
-    // four 16-bit code units hashed as they stand, candidates verified on the UTF-16 HBM-table program (lower_filter_wide).  Without it these
-    // rows take hot rows + HBM table: 9.3 ms on the 10M-row batch where the one-page route runs at 1.1.  NEEDLE_PREFILTER_WIDE=0: never.
-    if (v->char_width == 2 && u16.page < 0 && wide_filter_wanted(fp->prog.hdr.mode) && op != OP_MATCHES && !d_from && !d_end_state && !no_backward &&
-        dict_env == 0 && v->row_stride * 2 < 8 * (uint64_t)kStripeBytes) {
-        const DevProgram *tp = nullptr;
-        rc = filter_route_wide(p, op, which, &tp);
-        if (rc) return rc;
-        if (tp) {
-            const ScanArgs a = filter_scan_args(v, v->row_stride /* chars */, tp, op == OP_FIND ? p->t.fixed_len : -1, d_bitmap, d_start, d_end, d_packed, packed8);
-            if (ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, tp->prog.ng.p) && ngram_watch_allows(p, tp)) {
-                HIP_TRY(launch_ngram(op, a, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream, 2, 0, 0));
-                HIP_TRY(ngram_watch_after_launch(tp, (hipStream_t)stream));
-                return NEEDLE_OK;
-            }
-        }
-    }
-    if (d_end_state && (fp->prog.hdr.mode == MODE_HYBRID || fp->prog.hdr.mode == MODE_SPARSE)) {
-        // the speculative-stripe pass wants every stripe's end state in the numbering of the HBM-table layout its fix-up
-        // kernel walks (variant 3); the hot-rows and compressed forms number / encode states their own way
-        rc = get_program(p, which, (int)v->char_width, 3, &fp, &n_cus);
-        if (rc) return rc;
-    }
-    if (!d_end_state && wants_stripe_path(v, fp->prog.hdr, d_from != nullptr)) return run_stripe_path(p, op, v, fp, n_cus, d_bitmap, d_start, d_end, stream);
-    if (!d_end_state && !d_from && fp->prog.hdr.mode != MODE_PACK) {
-        bool done = false;
-        rc = run_speculative_stripes(p, op, v, d_bitmap, d_start, d_end, stream, &done);
-        if (rc || done) return rc;
-    }
-    // the tiled kernel forms per-lane row offsets in 32 bits (up to 63 x stride); only the stripe path above takes
-    // rows of tens of megabytes and more
-    if (v->row_stride * v->char_width >= (1ull << 26))
-        return fail(NEEDLE_ERR_UNSUPPORTED, "rows of 64 MiB or more are only supported on the stripe paths (automata of at most 5 states, or ones that re-synchronise; not with NEEDLE_LONG_ROWS=0, per-row cursors or empty-matching patterns)");
-    // An automaton that fits the LDS in no form (hot rows + HBM table, or the HBM table alone): containedIn() / find() behind the
-    // n-gram candidate filter with the verify walks out of HBM / L2 (lower_filter_hbm) -- the per-char walk of such an automaton
-    // collapses on text that leaves the hot states (near-miss rows: 20 ms on the 10M-row batch), the filter's does not.
-    if ((fp->prog.hdr.mode == MODE_HYBRID || fp->prog.hdr.mode == MODE_GLOBAL) && v->char_width == 1 && op != OP_MATCHES && !d_from && !d_end_state &&
-        !no_backward && ngram_level() > 0 && dict_env == 0) {
-        // (find() without bounded match lengths, no lengths form: the forward search automaton + backward walks for the starts, variant 12)
-        const DevProgram *tp = nullptr, *bwp = nullptr;
-        rc = filter_route_hbm(p, op, which, need_backward, true, &tp, &bwp);
-        if (rc) return rc;
-        if (tp) {
-            ScanArgs a = filter_scan_args(v, v->row_stride, tp, op == OP_FIND ? p->t.fixed_len : -1, d_bitmap, d_start, d_end, d_packed, packed8);
-            if (bwp) a.bprog = bwp->d_blob, a.bhdr = bwp->prog.hdr;
-            if (ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, tp->prog.ng.p) && ngram_watch_allows(p, tp)) {
-                HIP_TRY(launch_ngram(op, a, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream));
-                HIP_TRY(ngram_watch_after_launch(tp, (hipStream_t)stream));
-                return NEEDLE_OK;
-            }
-        }
-    }
-    // find() whose pattern allows it: the "lengths" automaton -- the state the walk stops in remembers how long the match was,
-    // start = end - pend[state], no indexBackwards, no text snapshots (needle_lower.h).  Taken where the ordinary program is a
-    // plain LDS table (the modes pend[] can be indexed in).  NEEDLE_FIND_LENGTHS=0: off (A/B, tests).
-    bool lengths_form = false;
-    if (need_backward && !d_end_state && !no_backward && find_lengths_for(fp->prog.hdr.mode)) {
-        const DevProgram *lp = nullptr;
-        rc = get_program(p, W_FORWARDS, (int)v->char_width, 7, &lp, nullptr);
-        if (rc) return rc;
-        // (a pair-table automaton whose lengths program no longer fits the pair table keeps its two walks: two chars per lookup
-        // beat the saved backward walk -- NEEDLE_FIND_LENGTHS=2 takes the plain table all the same)
-        static const bool force_tables = getenv("NEEDLE_FIND_LENGTHS") && atoi(getenv("NEEDLE_FIND_LENGTHS")) > 1;
-        if (lp && fp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR && !force_tables) lp = nullptr;
-        if (lp) fp = lp, lengths_form = true;
-    }
-    ScanArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rows = (const uint8_t *)v->rows;
-    a.n_rows = v->n_rows;
-    a.stride_bytes = v->row_stride * v->char_width;
-    a.total_bytes = a.n_rows * a.stride_bytes;
-    a.row_len = v->row_len;
-    a.lengths = v->lengths;
-    a.from = d_from;
-    a.prog = fp->d_blob;
-    a.hdr = fp->prog.hdr;
-    a.fixed_len = -1;
-    if (op == OP_FIND) {
-        a.fixed_len = p->t.fixed_len;
-        if (a.fixed_len < 0 && !lengths_form) {
-            rc = get_program(p, W_BACKWARDS, (int)v->char_width, 1, &bp, nullptr);
+    const ScanOut out{d_bitmap, d_start, d_end, d_packed, packed8};
+    const int32_t fixed_len = op == OP_FIND ? p->t.fixed_len : -1;
+    RouteCaps caps;
+    caps.filter = !d_from && !d_end_state && !no_backward;
+    caps.stand_in = dict_env == 0;
+    caps.utf16 = v->row_stride * 2 < 8 * (uint64_t)kStripeBytes; // (longer rows: the stripe paths')
+    caps.lengths_form = !d_end_state && !no_backward;
+    // (UTF-16 rows behind a byte program or the WIDE one: the stride in CHARS; 8-bit rows: the same number)
+    auto try_filter = [&](const Route &c, bool *launched) {
+        return launch_filter(p, op, scan_args(v, v->row_stride, c.fp, c.bp, fixed_len, out), c.fp, c.n_cus, stream, cw, c.page, c.sub, launched);
+    };
+    // Few long rows, once the ordinary program is known: function composition across stripes (packed-mode automata), speculative stripes (the
+    // others); what is left walks its rows one lane each.
+    auto stripe_paths = [&](Route *r, bool *done) -> int {
+        if (d_end_state && (r->fp->prog.hdr.mode == MODE_HYBRID || r->fp->prog.hdr.mode == MODE_SPARSE)) {
+            // the speculative-stripe pass wants every stripe's end state in the numbering of the HBM-table layout its fix-up
+            // kernel walks; the hot-rows and compressed forms number / encode states their own way
+            int rc = get_program(p, which_of(op), cw, V_HBM_TABLE, &r->fp, &r->n_cus);
             if (rc) return rc;
-            a.bprog = bp->d_blob;
-            a.bhdr = bp->prog.hdr;
         }
-    }
-    a.bitmap = d_bitmap;
-    a.start = d_start;
-    a.end = d_end;
-    a.packed = d_packed;
-    a.packed8 = packed8 ? 1u : 0u;
+        if (!d_end_state && wants_stripe_path(v, r->fp->prog.hdr, d_from != nullptr)) {
+            *done = true;
+            return run_stripe_path(p, op, v, r->fp, r->n_cus, d_bitmap, d_start, d_end, stream_);
+        }
+        if (!d_end_state && !d_from && r->fp->prog.hdr.mode != MODE_PACK) {
+            // (pass 1: every stripe as a row of its own, through this function again)
+            auto scan_stripes = [&](const needle_batch_view *sv, uint64_t *bm, int32_t *st, int32_t *en, uint32_t *end_state) {
+                return run_dev(cp, op, sv, bm, st, en, stream_, nullptr, end_state, true);
+            };
+            int rc = run_speculative_stripes(p, op, v, d_bitmap, d_start, d_end, stream_, done, scan_stripes);
+            if (rc || *done) return rc;
+        }
+        // the tiled kernel forms per-lane row offsets in 32 bits (up to 63 x stride); only the stripe paths above take
+        // rows of tens of megabytes and more
+        if (stride_bytes >= (1ull << 26))
+            return fail(NEEDLE_ERR_UNSUPPORTED, "rows of 64 MiB or more are only supported on the stripe paths (automata of at most 5 states, or ones that re-synchronise; not with NEEDLE_LONG_ROWS=0, per-row cursors or empty-matching patterns)");
+        return NEEDLE_OK;
+    };
+    Route r;
+    rc = choose_route(p, op, cw, caps, try_filter, stripe_paths, &r);
+    if (rc || r.kind != Route::SCAN) return rc;
+    ScanArgs a = scan_args(v, stride_bytes, r.fp, r.bp, fixed_len, out);
+    a.from = d_from;
     a.end_state = d_end_state;
     bool skip_backward = no_backward; // (speculative pass: only lastMatch is wanted)
 #ifdef NEEDLE_TUNING // measurement builds only (scripts/build_tuning.sh): a switch that changes ANSWERS (start = end) never ships
-    static const bool dbg_no_backward = getenv("NEEDLE_DEBUG_NO_BACKWARD") != nullptr;
-    skip_backward = skip_backward || dbg_no_backward;
+    skip_backward = skip_backward || debug_no_backward();
 #endif
     if (skip_backward && op == OP_FIND) a.fixed_len = 0, a.bprog = nullptr;
 #ifdef NEEDLE_TUNING
@@ -944,25 +1009,11 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
     // ordinary kernel on what is left; find()'s starts by indexBackwards afterwards, one lane per matched row.
     // Measurement builds only (scripts/build_tuning.sh).  NEEDLE_DICT: 0 off (default: measured, it is no faster -- DESIGN.md s4),
     // 1 on for the compressed automaton, 2 also for plain uint16 LDS tables.
-    if (dict_env > 0 && !lengths_form && (a.hdr.mode == MODE_SPARSE || dict_env > 1) && dict_kernel_applies((int)v->char_width, a)) {
-        HIP_TRY(launch_dict(op, a, n_cus, (hipStream_t)stream));
+    if (dict_env > 0 && !r.lengths_form && (a.hdr.mode == MODE_SPARSE || dict_env > 1) && dict_kernel_applies(cw, a)) {
+        HIP_TRY(launch_dict(op, a, r.n_cus, stream));
         const uint64_t done_rows = (a.n_rows >> 7) << 7;
         if (op == OP_FIND && a.fixed_len < 0 && done_rows) {
-            StripeArgs ba;
-            memset(&ba, 0, sizeof(ba));
-            ba.rows = a.rows;
-            ba.n_rows = done_rows;
-            ba.stride_bytes = a.stride_bytes;
-            ba.prog = fp->d_blob;
-            ba.hdr = fp->prog.hdr;
-            ba.bitmap = d_bitmap;
-            ba.start = d_start;
-            ba.end = d_end;
-            ba.fixed_len = -1;
-            ba.op = OP_FIND;
-            ba.bprog = bp->d_blob;
-            ba.bhdr = bp->prog.hdr;
-            HIP_TRY(launch_backward_rows((int)v->char_width, ba, (hipStream_t)stream));
+            HIP_TRY(launch_find_starts(cw, a.rows, done_rows, a.stride_bytes, r.fp, r.bp, -1, d_bitmap, d_start, d_end, stream));
         }
         if (done_rows == a.n_rows) return NEEDLE_OK;
         a.rows += done_rows * a.stride_bytes; // the last n_rows % 128 rows
@@ -974,20 +1025,34 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
 #endif
     // The n-gram candidate filter (needle_ngram.hip): the automaton only runs where a hashed 4-byte window of the
     // text can stand ahead of a match.  For programs whose lowering established that this gives the reference's answers
-    // (needle_ngram_host.cpp), on containedIn() and on find() whose start is end - length (lengths programs, one-length patterns).
-    // (find() of a pattern WITHOUT bounded match lengths -- `(kw1|..|kw1000)[0-9]+` -- takes it too: its verified candidates find their
-    // starts by indexBackwards, the lock-step backward walk on text out of L2.  NEEDLE_PREFILTER_UNBOUNDED=0: the scan kernel)
-    static const bool unbounded_on = !(getenv("NEEDLE_PREFILTER_UNBOUNDED") && atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) == 0);
-    const bool by_backward_walk = op == OP_FIND && a.fixed_len < 0 && !lengths_form && a.bprog != nullptr && unbounded_on && !d_from;
-    if (fp->d_ng && fp->prog.ng.p.on && ngram_level() > 0 && v->char_width == 1 && op != OP_MATCHES && !skip_backward &&
-        (op == OP_CONTAINED_IN || lengths_form || a.fixed_len >= 0 || by_backward_walk) && ngram_shape_ok(a) && ngram_lds_bytes(a.hdr, fp->prog.ng.p)) {
-        if (ngram_watch_allows(p, fp)) {
-            HIP_TRY(launch_ngram(op, a, fp->prog.ng.p, fp->d_ng, fp->d_ng_stats, n_cus, (hipStream_t)stream));
-            HIP_TRY(ngram_watch_after_launch(fp, (hipStream_t)stream));
-            return NEEDLE_OK;
-        }
+    // (needle_ngram_host.cpp), on containedIn() and on find() whose start is end - length (lengths programs, one-length patterns) or
+    // comes from a backward walk (choose_route, route 6).
+    if (r.own_filter && !skip_backward) {
+        bool launched = false;
+        rc = launch_filter(p, op, a, r.fp, r.n_cus, stream, 1, 0, 0xFF, &launched);
+        if (rc || launched) return rc;
     }
-    HIP_TRY(launch_scan(op, (int)v->char_width, a, n_cus, (hipStream_t)stream));
+    HIP_TRY(launch_scan(op, cw, a, r.n_cus, stream));
+    return NEEDLE_OK;
+}
+
+// The "more" flag of a one-pass find-all launch: a zeroed scratch word the kernel sets when some row has a match beyond its last slot.
+// launch(d_more) enqueues the kernel (and what belongs behind it); the flag is read back -- the call's only synchronisation -- only when the
+// caller asked whether its slots sufficed (more != nullptr).
+template <class Launch>
+static int with_more_flag(hipStream_t stream, int *more, const char *what, Launch &&launch) {
+    int32_t *d_more = nullptr;
+    HIP_TRY(scratch_malloc((void **)&d_more, 16, stream));
+    hipError_t e = hipMemsetAsync(d_more, 0, 4, stream);
+    if (e == hipSuccess) e = launch(d_more);
+    int32_t m = 0;
+    if (e == hipSuccess && more) {
+        e = hipMemcpyAsync(&m, d_more, 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    }
+    (void)scratch_free(d_more, stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (more) *more = m != 0;
     return NEEDLE_OK;
 }
 
@@ -1080,103 +1145,154 @@ static int run_host_small(const needle_pattern *p, int op, const needle_batch_vi
     return NEEDLE_OK;
 }
 
-// Host-buffer convenience: pad rows to a 16-byte stride, upload, run, download.
-static int run_host_one(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t *bitmap, int32_t *start,
-                        int32_t *end);
+// The device allocations of one host convenience call: whatever it holds is freed on every return path.
+struct DevAllocs {
+    std::vector<void *> held;
+    DevAllocs() = default;
+    DevAllocs(const DevAllocs &) = delete;
+    DevAllocs &operator=(const DevAllocs &) = delete;
+    ~DevAllocs() {
+        for (void *q : held) (void)hipFree(q);
+    }
+    template <class T>
+    hipError_t alloc(T **out, size_t bytes) {
+        const hipError_t e = hipMalloc((void **)out, bytes);
+        if (e == hipSuccess) held.push_back((void *)*out);
+        return e;
+    }
+};
 
-// Host batches of any size: at most kHostChunkBytes of rows are resident on the device at a time (chunks start on
-// 64-row boundaries, so every chunk owns whole bitmap words).
-static int run_host(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t *bitmap, int32_t *start,
-                    int32_t *end) {
-    int rc = check_view(v, false);
-    if (rc) return rc;
-    if ((rc = check_host_lengths(v))) return rc;
-    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
-    const uint64_t row_bytes = std::max<uint64_t>(16, (v->row_stride * v->char_width + 15) & ~(uint64_t)15);
-    uint64_t per = std::max<uint64_t>(64, (kHostChunkBytes / row_bytes) & ~(uint64_t)63);
-    if (v->n_rows <= per) return run_host_one(p, op, v, bitmap, start, end);
+// The rows of a host batch on the device, padded to a stride of whole 16 bytes (zero-filled), and their lengths (d_len: not used without
+// lengths).  *dv: the batch as a device view.
+static uint64_t padded_stride_bytes(const needle_batch_view *v) { return std::max<uint64_t>(16, (v->row_stride * v->char_width + 15) & ~(uint64_t)15); }
+static hipError_t upload_rows(const needle_batch_view *v, void *d_rows, uint32_t *d_len, needle_batch_view *dv) {
+    const uint64_t src_stride = v->row_stride * v->char_width, dst_stride = padded_stride_bytes(v);
+    hipError_t e = hipSuccess;
+    if (dst_stride == src_stride) {
+        e = hipMemcpy(d_rows, v->rows, v->n_rows * src_stride, hipMemcpyHostToDevice);
+    } else {
+        e = hipMemset(d_rows, 0, v->n_rows * dst_stride);
+        if (e == hipSuccess && src_stride) e = hipMemcpy2D(d_rows, dst_stride, v->rows, src_stride, src_stride, v->n_rows, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && v->lengths) e = hipMemcpy(d_len, v->lengths, v->n_rows * 4, hipMemcpyHostToDevice);
+    *dv = *v;
+    dv->rows = d_rows;
+    dv->lengths = v->lengths ? d_len : nullptr;
+    dv->row_stride = dst_stride / v->char_width;
+    return e;
+}
+
+// NEEDLE_HOST_CHUNK_BYTES: what the host entry points keep resident on the device at a time (tests shrink it).
+static uint64_t host_chunk_bytes() {
+    static const uint64_t v = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
+    return v;
+}
+// NEEDLE_HOST_RESULT_BYTES: the bound on the find-all results the host entry points keep resident on the device at a time (tests shrink it).
+static uint64_t host_result_bytes() {
+    static const uint64_t v = getenv("NEEDLE_HOST_RESULT_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_RESULT_BYTES")) : (512ull << 20);
+    return v;
+}
+
+// The fill pass of the CSR host entries over rows [r0, r1), whose counts stand summed up in `offsets`.  It runs over sub-ranges of the rows so
+// that the results resident on the device stay bounded too (NEEDLE_HOST_RESULT_BYTES): a dense-match batch (a one-char pattern over
+// 256-char rows files ~2 KiB per row) would otherwise ask for several times the chunk's row bytes in one allocation.
+// fill(a, n, d_csr, d_start, d_end, &more): the layout's fill of rows [a, a + n) at the sub-range's own offsets, uploaded to d_csr.
+template <class Fill>
+static int csr_fill_pass(const std::string &who, const uint64_t *offsets, uint64_t r0, uint64_t r1, uint8_t *d_csr, int32_t *start, int32_t *end,
+                         DevAllocs &dev, Fill &&fill) {
+    const uint64_t max_m = std::max<uint64_t>(host_result_bytes() / 8, 1);
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    std::vector<std::pair<uint64_t, uint64_t>> ranges; // [a, b): at least one row, at most max_m matches (one row may exceed it)
+    uint64_t biggest = 0;
+    for (uint64_t a = r0; a < r1;) {
+        uint64_t b = a + 1;
+        while (b < r1 && offsets[b + 1] - offsets[a] <= max_m) ++b;
+        ranges.emplace_back(a, b);
+        biggest = std::max<uint64_t>(biggest, offsets[b] - offsets[a]);
+        a = b;
+    }
+    uint8_t *d_out = nullptr; // start | end
+    hipError_t e = dev.alloc(&d_out, 2 * up16(biggest * 4) + 16);
+    if (e != hipSuccess) return hip_fail(e, (who + " results").c_str());
+    std::vector<uint64_t> local;
+    for (const auto &rg : ranges) {
+        const uint64_t a = rg.first, sn = rg.second - rg.first, m = offsets[rg.second] - offsets[a];
+        if (m == 0) continue;
+        local.resize(sn + 1);
+        for (uint64_t r = 0; r <= sn; ++r) local[r] = offsets[a + r] - offsets[a];
+        e = hipMemcpy(d_csr, local.data(), (sn + 1) * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, (who + " offsets").c_str());
+        int more = 0;
+        int rc = fill(a, sn, (const uint64_t *)d_csr, (int32_t *)d_out, (int32_t *)(d_out + up16(biggest * 4)), &more);
+        if (rc) return rc;
+        if (more) return fail(NEEDLE_ERR_DEVICE, who + ": count pass and fill pass disagree");
+        e = hipMemcpy(start + offsets[a], d_out, m * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(end + offsets[a], d_out + up16(biggest * 4), m * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, (who + " download").c_str());
+    }
+    return NEEDLE_OK;
+}
+
+// Host batches of any size: run(chunk, r0) for consecutive row chunks of at most NEEDLE_HOST_CHUNK_BYTES on the device -- a row costs its
+// padded text + per_row bytes there -- that start on 64-row boundaries, so every chunk owns whole bitmap words.
+template <class Run>
+static int for_host_chunks(const needle_batch_view *v, uint64_t per_row, Run &&run) {
+    const uint64_t per = std::max<uint64_t>(64, (host_chunk_bytes() / (padded_stride_bytes(v) + per_row)) & ~(uint64_t)63);
     for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
         needle_batch_view c = *v;
         c.n_rows = std::min<uint64_t>(per, v->n_rows - r0);
         c.rows = (const uint8_t *)v->rows + r0 * v->row_stride * v->char_width;
         c.lengths = v->lengths ? v->lengths + r0 : nullptr;
-        rc = run_host_one(p, op, &c, bitmap ? bitmap + r0 / 64 : nullptr, start ? start + r0 : nullptr, end ? end + r0 : nullptr);
+        int rc = run(c, r0);
         if (rc) return rc;
     }
     return NEEDLE_OK;
 }
 
+// Host-buffer convenience: pad rows to a 16-byte stride, upload, run, download.
 static int run_host_one(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t *bitmap, int32_t *start,
                         int32_t *end) {
     int rc = check_view(v, false);
     if (rc) return rc;
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
-    const size_t cw = v->char_width;
-    const uint64_t src_stride = v->row_stride * cw;
-    uint64_t dst_stride = (src_stride + 15) & ~(uint64_t)15;
-    if (dst_stride == 0) dst_stride = 16;
+    const uint64_t dst_stride = padded_stride_bytes(v);
     const size_t words = (v->n_rows + 63) / 64;
     if (op == OP_FIND && (!start || !end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
     if (v->n_rows * dst_stride + v->n_rows * 16 <= kSmallHostBatchBytes) return run_host_small(p, op, v, dst_stride, bitmap, start, end);
+    DevAllocs dev;
     uint8_t *d_rows = nullptr;
     uint32_t *d_len = nullptr;
     uint64_t *d_bm = nullptr;
     int32_t *d_s = nullptr, *d_e = nullptr;
-    auto cleanup = [&]() {
-        if (d_rows) (void)hipFree(d_rows);
-        if (d_len) (void)hipFree(d_len);
-        if (d_bm) (void)hipFree(d_bm);
-        if (d_s) (void)hipFree(d_s);
-        if (d_e) (void)hipFree(d_e);
-    };
-#define HIP_TRY_C(expr)                                    \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) {                            \
-            cleanup();                                     \
-            return hip_fail(_e, #expr);                    \
-        }                                                  \
-    } while (0)
-    HIP_TRY_C(hipMalloc((void **)&d_rows, v->n_rows * dst_stride));
-    if (dst_stride == src_stride) {
-        HIP_TRY_C(hipMemcpy(d_rows, v->rows, v->n_rows * src_stride, hipMemcpyHostToDevice));
-    } else {
-        HIP_TRY_C(hipMemset(d_rows, 0, v->n_rows * dst_stride));
-        if (src_stride)
-            HIP_TRY_C(hipMemcpy2D(d_rows, dst_stride, v->rows, src_stride, src_stride, v->n_rows, hipMemcpyHostToDevice));
-    }
-    if (v->lengths) {
-        HIP_TRY_C(hipMalloc((void **)&d_len, v->n_rows * 4));
-        HIP_TRY_C(hipMemcpy(d_len, v->lengths, v->n_rows * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY_C(hipMalloc((void **)&d_bm, words * 8));
+    needle_batch_view dv;
+    HIP_TRY(dev.alloc(&d_rows, v->n_rows * dst_stride));
+    if (v->lengths) HIP_TRY(dev.alloc(&d_len, v->n_rows * 4));
+    HIP_TRY(upload_rows(v, d_rows, d_len, &dv));
+    HIP_TRY(dev.alloc(&d_bm, words * 8));
     if (op == OP_FIND) {
-        if (!start || !end) {
-            cleanup();
-            return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
-        }
-        HIP_TRY_C(hipMalloc((void **)&d_s, v->n_rows * 4));
-        HIP_TRY_C(hipMalloc((void **)&d_e, v->n_rows * 4));
+        HIP_TRY(dev.alloc(&d_s, v->n_rows * 4));
+        HIP_TRY(dev.alloc(&d_e, v->n_rows * 4));
     }
-    needle_batch_view dv = *v;
-    dv.rows = d_rows;
-    dv.lengths = d_len;
-    dv.row_stride = dst_stride / cw;
     rc = run_dev(p, op, &dv, d_bm, d_s, d_e, nullptr);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    HIP_TRY_C(hipDeviceSynchronize());
-    HIP_TRY_C(hipMemcpy(bitmap, d_bm, words * 8, hipMemcpyDeviceToHost));
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(bitmap, d_bm, words * 8, hipMemcpyDeviceToHost));
     if (op == OP_FIND) {
-        HIP_TRY_C(hipMemcpy(start, d_s, v->n_rows * 4, hipMemcpyDeviceToHost));
-        HIP_TRY_C(hipMemcpy(end, d_e, v->n_rows * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(start, d_s, v->n_rows * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(end, d_e, v->n_rows * 4, hipMemcpyDeviceToHost));
     }
-    cleanup();
     return NEEDLE_OK;
-#undef HIP_TRY_C
+}
+
+static int run_host(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t *bitmap, int32_t *start,
+                    int32_t *end) {
+    int rc = check_view(v, false);
+    if (rc) return rc;
+    if ((rc = check_host_lengths(v))) return rc;
+    return for_host_chunks(v, 0, [&](const needle_batch_view &c, uint64_t r0) {
+        return run_host_one(p, op, &c, bitmap ? bitmap + r0 / 64 : nullptr, start ? start + r0 : nullptr, end ? end + r0 : nullptr);
+    });
 }
 
 static int check_packed(const needle_packed_view *v) {
@@ -1186,8 +1302,73 @@ static int check_packed(const needle_packed_view *v) {
     return NEEDLE_OK;
 }
 
-static int run_packed_host_one(const needle_pattern *p, int op, const needle_packed_view *v, uint64_t *bitmap,
-                               int32_t *start, int32_t *end);
+static int check_packed_dev(const needle_pattern *p, const needle_packed_view *v) {
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    return NEEDLE_OK;
+}
+
+// The offsets of a packed HOST batch (readable here): non-decreasing; *max_len = its longest row, in chars.
+static int check_packed_host_offsets(const needle_packed_view *v, uint64_t *max_len) {
+    *max_len = 0;
+    for (uint64_t r = 0; r < v->n_rows; ++r) {
+        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
+        *max_len = std::max<uint64_t>(*max_len, v->offsets[r + 1] - v->offsets[r]);
+    }
+    return NEEDLE_OK;
+}
+
+// One packed host batch (checked by run_packed_host: rows of up to max_len chars) as fixed-stride rows: upload, unpack on the device, run, download.
+static int run_packed_host_one(const needle_pattern *p, int op, const needle_packed_view *v, uint64_t max_len, uint64_t *bitmap,
+                               int32_t *start, int32_t *end) {
+    const uint64_t cw = v->char_width;
+    if (max_len > 0xFFFFFFFFull) return fail(NEEDLE_ERR_INVALID, "row longer than 2^32 - 1 chars");
+    const uint64_t total_chars = v->offsets[v->n_rows];
+    if (total_chars && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
+    uint64_t stride_bytes = (max_len * cw + 15) & ~(uint64_t)15;
+    if (stride_bytes == 0) stride_bytes = 16;
+    const size_t words = (v->n_rows + 63) / 64;
+    DevAllocs dev;
+    void *d_data = nullptr, *d_rows = nullptr;
+    uint64_t *d_off = nullptr, *d_bm = nullptr;
+    uint32_t *d_len = nullptr;
+    int32_t *d_s = nullptr, *d_e = nullptr;
+    const size_t data_bytes = (size_t)((total_chars * cw + 3) & ~(uint64_t)3);
+    HIP_TRY(dev.alloc(&d_data, data_bytes ? data_bytes : 4));
+    if (total_chars) HIP_TRY(hipMemcpy(d_data, v->data, (size_t)(total_chars * cw), hipMemcpyHostToDevice));
+    HIP_TRY(dev.alloc(&d_off, (v->n_rows + 1) * 8));
+    HIP_TRY(hipMemcpy(d_off, v->offsets, (v->n_rows + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(dev.alloc(&d_rows, v->n_rows * stride_bytes));
+    HIP_TRY(dev.alloc(&d_len, v->n_rows * 4));
+    HIP_TRY(dev.alloc(&d_bm, words * 8));
+    if (op == OP_FIND) {
+        HIP_TRY(dev.alloc(&d_s, v->n_rows * 4));
+        HIP_TRY(dev.alloc(&d_e, v->n_rows * 4));
+    }
+    needle_packed_view dpv = *v;
+    dpv.data = d_data;
+    dpv.offsets = d_off;
+    int rc = needle_rows_from_packed_dev(&dpv, d_rows, stride_bytes / cw, d_len, nullptr, nullptr);
+    if (rc) return rc;
+    needle_batch_view bv;
+    memset(&bv, 0, sizeof(bv));
+    bv.rows = d_rows;
+    bv.char_width = v->char_width;
+    bv.n_rows = v->n_rows;
+    bv.row_stride = stride_bytes / cw;
+    bv.lengths = d_len;
+    rc = run_dev(p, op, &bv, d_bm, d_s, d_e, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(bitmap, d_bm, words * 8, hipMemcpyDeviceToHost));
+    if (op == OP_FIND) {
+        HIP_TRY(hipMemcpy(start, d_s, v->n_rows * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(end, d_e, v->n_rows * 4, hipMemcpyDeviceToHost));
+    }
+    return NEEDLE_OK;
+}
 
 // Packed host batch.  The fixed-stride layout the kernels read pads every row to the longest one: harmless when the
 // lengths are alike, ruinous when one 1 MB document sits among a million 40-char strings.  Rows are therefore grouped
@@ -1203,14 +1384,11 @@ static int run_packed_host(const needle_pattern *p, int op, const needle_packed_
     if (op == OP_FIND && (!start || !end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
     const uint64_t cw = v->char_width, n = v->n_rows;
     uint64_t max_len = 0;
-    for (uint64_t r = 0; r < n; ++r) {
-        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
-        max_len = std::max<uint64_t>(max_len, v->offsets[r + 1] - v->offsets[r]);
-    }
+    if ((rc = check_packed_host_offsets(v, &max_len))) return rc;
     if (v->offsets[n] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
     const uint64_t total_bytes = v->offsets[n] * cw;
     const uint64_t padded = n * std::max<uint64_t>(16, (max_len * cw + 15) & ~(uint64_t)15);
-    if (padded <= 4 * total_bytes + (64u << 10)) return run_packed_host_one(p, op, v, bitmap, start, end);
+    if (padded <= 4 * total_bytes + (64u << 10)) return run_packed_host_one(p, op, v, max_len, bitmap, start, end);
     auto klass = [&](uint64_t len_chars) { // smallest k with len * cw <= 64 << 2k
         int k = 0;
         while ((len_chars * cw) > (64ull << (2 * k))) ++k;
@@ -1226,7 +1404,12 @@ static int run_packed_host(const needle_pattern *p, int op, const needle_packed_
     for (const auto &ids : rows_of) {
         if (ids.empty()) continue;
         off.assign(ids.size() + 1, 0);
-        for (size_t i = 0; i < ids.size(); ++i) off[i + 1] = off[i] + (v->offsets[ids[i] + 1] - v->offsets[ids[i]]);
+        uint64_t longest = 0;
+        for (size_t i = 0; i < ids.size(); ++i) {
+            const uint64_t len = v->offsets[ids[i] + 1] - v->offsets[ids[i]];
+            off[i + 1] = off[i] + len;
+            longest = std::max(longest, len);
+        }
         data.resize((size_t)(off.back() * cw));
         for (size_t i = 0; i < ids.size(); ++i)
             memcpy(data.data() + off[i] * cw, (const uint8_t *)v->data + v->offsets[ids[i]] * cw, (size_t)((off[i + 1] - off[i]) * cw));
@@ -1240,7 +1423,7 @@ static int run_packed_host(const needle_pattern *p, int op, const needle_packed_
             st.assign(ids.size(), -1);
             en.assign(ids.size(), -1);
         }
-        rc = run_packed_host_one(p, op, &sub, bm.data(), st.data(), en.data());
+        rc = run_packed_host_one(p, op, &sub, longest, bm.data(), st.data(), en.data());
         if (rc) return rc;
         for (size_t i = 0; i < ids.size(); ++i) {
             if ((bm[i >> 6] >> (i & 63)) & 1) bitmap[ids[i] >> 6] |= 1ull << (ids[i] & 63);
@@ -1253,210 +1436,59 @@ static int run_packed_host(const needle_pattern *p, int op, const needle_packed_
     return NEEDLE_OK;
 }
 
-static int run_packed_host_one(const needle_pattern *p, int op, const needle_packed_view *v, uint64_t *bitmap,
-                               int32_t *start, int32_t *end) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
-    if (op == OP_FIND && (!start || !end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
-    const uint64_t cw = v->char_width;
-    uint64_t max_len = 0;
-    for (uint64_t r = 0; r < v->n_rows; ++r) {
-        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
-        max_len = std::max<uint64_t>(max_len, v->offsets[r + 1] - v->offsets[r]);
-    }
-    if (max_len > 0xFFFFFFFFull) return fail(NEEDLE_ERR_INVALID, "row longer than 2^32 - 1 chars");
-    const uint64_t total_chars = v->offsets[v->n_rows];
-    if (total_chars && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    uint64_t stride_bytes = (max_len * cw + 15) & ~(uint64_t)15;
-    if (stride_bytes == 0) stride_bytes = 16;
-    const size_t words = (v->n_rows + 63) / 64;
-    void *d_data = nullptr, *d_rows = nullptr;
-    uint64_t *d_off = nullptr, *d_bm = nullptr;
-    uint32_t *d_len = nullptr;
-    int32_t *d_s = nullptr, *d_e = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {d_data, d_rows, (void *)d_off, (void *)d_bm, (void *)d_len, (void *)d_s, (void *)d_e})
-            if (q) (void)hipFree(q);
-    };
-#define HIP_TRY_C(expr)                                    \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) {                            \
-            cleanup();                                     \
-            return hip_fail(_e, #expr);                    \
-        }                                                  \
-    } while (0)
-    const size_t data_bytes = (size_t)((total_chars * cw + 3) & ~(uint64_t)3);
-    HIP_TRY_C(hipMalloc(&d_data, data_bytes ? data_bytes : 4));
-    if (total_chars) HIP_TRY_C(hipMemcpy(d_data, v->data, (size_t)(total_chars * cw), hipMemcpyHostToDevice));
-    HIP_TRY_C(hipMalloc((void **)&d_off, (v->n_rows + 1) * 8));
-    HIP_TRY_C(hipMemcpy(d_off, v->offsets, (v->n_rows + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY_C(hipMalloc(&d_rows, v->n_rows * stride_bytes));
-    HIP_TRY_C(hipMalloc((void **)&d_len, v->n_rows * 4));
-    HIP_TRY_C(hipMalloc((void **)&d_bm, words * 8));
-    if (op == OP_FIND) {
-        HIP_TRY_C(hipMalloc((void **)&d_s, v->n_rows * 4));
-        HIP_TRY_C(hipMalloc((void **)&d_e, v->n_rows * 4));
-    }
-    needle_packed_view dpv = *v;
-    dpv.data = d_data;
-    dpv.offsets = d_off;
-    rc = needle_rows_from_packed_dev(&dpv, d_rows, stride_bytes / cw, d_len, nullptr, nullptr);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    needle_batch_view bv;
-    memset(&bv, 0, sizeof(bv));
-    bv.rows = d_rows;
-    bv.char_width = v->char_width;
-    bv.n_rows = v->n_rows;
-    bv.row_stride = stride_bytes / cw;
-    bv.lengths = d_len;
-    rc = run_dev(p, op, &bv, d_bm, d_s, d_e, nullptr);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    HIP_TRY_C(hipDeviceSynchronize());
-    HIP_TRY_C(hipMemcpy(bitmap, d_bm, words * 8, hipMemcpyDeviceToHost));
-    if (op == OP_FIND) {
-        HIP_TRY_C(hipMemcpy(start, d_s, v->n_rows * 4, hipMemcpyDeviceToHost));
-        HIP_TRY_C(hipMemcpy(end, d_e, v->n_rows * 4, hipMemcpyDeviceToHost));
-    }
-    cleanup();
-    return NEEDLE_OK;
-#undef HIP_TRY_C
-}
-
-// Packed device batches scanned as they lie (needle_packed.h): no conversion to fixed-stride rows, no host synchronisation.  The
-// program is chosen as run_dev's scan-kernel path chooses it -- the lengths form where find_lengths_for() allows it, else the
-// backward program -- so that one lowering serves both layouts and the answers are the same.  That is also the program run_dev
-// walks for per-row cursors (needle_find_next_dev: none of its filters or stripe paths take cursors).
+// Packed device batches scanned as they lie (needle_packed.h): no conversion to fixed-stride rows, no host synchronisation.  The route --
+// the program, and whether the n-gram candidate filter (needle_ngram_packed.h) runs in front of it -- is choose_route's, as for fixed-stride
+// rows: one lowering serves both layouts, with the same flood watch, the same counters and the same needle_pattern_set_prefilter pin.
+// What is this layout's own is listed there.  NEEDLE_PREFILTER_PACKED=0: packed rows never take the filter (A/B).
 // find() only: d_from = per-row cursors (needle_find_next_packed_dev); d_packed = the result as one dword per row, or one uint16 with
 // packed8 (needle_find_packed{16,8}_packed_dev: start / end are not used), d_overflow = optional flag of rows that escaped that form.
 static int run_packed_dev(const needle_pattern *cp, int op, const needle_packed_view *v, uint64_t *d_bitmap, int32_t *d_start,
-                          int32_t *d_end, void *stream, const int32_t *d_from = nullptr, uint32_t *d_packed = nullptr, bool packed8 = false,
+                          int32_t *d_end, void *stream_, const int32_t *d_from = nullptr, uint32_t *d_packed = nullptr, bool packed8 = false,
                           int32_t *d_overflow = nullptr) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
+    int rc = check_packed_dev(p, v);
     if (rc) return rc;
-    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
     if (!d_bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
     if (op == OP_FIND && !d_packed && (!d_start || !d_end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
     if (v->n_rows == 0) return NEEDLE_OK;
-    const int which = op == OP_MATCHES ? W_MATCHES : op == OP_CONTAINED_IN ? W_CONTAINED_IN : W_FORWARDS;
+    hipStream_t stream = (hipStream_t)stream_;
     const int cw = (int)v->char_width;
-    const bool need_backward = op == OP_FIND && p->t.fixed_len < 0;
-    const DevProgram *fp = nullptr;
-    int n_cus = 0;
-    // The n-gram candidate filter in front of packed rows (needle_ngram_packed.h): the filter program is chosen exactly as run_dev chooses it
-    // for the same pattern and char width (filter_route_*; the LDS programs' own filter below), under the same conditions -- containedIn(),
-    // or find() with a lengths form or a fixed length; no cursors -- with the same flood watch and the same needle_pattern_set_prefilter
-    // pin: it is the same program with the same counters.  No shape gate: the kernel is right for any amount of text.  find() of a pattern
-    // without bounded match lengths (variant 12) has no packed form.  NEEDLE_PREFILTER_PACKED=0: packed rows never take the filter (A/B).
-    static const bool pf_packed_on = !(getenv("NEEDLE_PREFILTER_PACKED") && atoi(getenv("NEEDLE_PREFILTER_PACKED")) == 0);
-    const bool filter_ok = pf_packed_on && op != OP_MATCHES && !d_from && ngram_level() > 0;
-    // launches tp's filter when its LDS footprint fits and the watch allows it; false: the call goes on to the next route / the plain kernel
-    auto try_filter = [&](const DevProgram *tp, int page, int sub, bool *launched) -> int {
+    const ScanOut out{d_bitmap, d_start, d_end, d_packed, packed8};
+    const int32_t fixed_len = op == OP_FIND ? p->t.fixed_len : -1;
+    static const bool pf_packed_on = (getenv("NEEDLE_PREFILTER_PACKED") ? atoi(getenv("NEEDLE_PREFILTER_PACKED")) : 1) != 0;
+    RouteCaps caps;
+    caps.filter = pf_packed_on && !d_from;
+    caps.unbounded_find = false; // (the packed filter kernel has no backward walk)
+    // The packed filter tail: no shape gate -- the kernel is right for any amount of text -- but the modes it is instantiated for (the ones a
+    // filter is ever built on), a match length its slot key can hold (16 bits) and its LDS footprint; then the flood watch, LAST.
+    auto try_filter = [&](const Route &c, bool *launched) -> int {
         *launched = false;
-        const uint32_t m = tp->prog.hdr.mode; // (the modes the packed filter kernel is instantiated for: the ones a filter is ever built on)
+        const DevProgram *tp = c.fp;
+        const uint32_t m = tp->prog.hdr.mode;
         if (m != MODE_TABLE8 && m != MODE_TABLE16 && m != MODE_SPARSE && m != MODE_GLOBAL) return NEEDLE_OK;
-        if (op == OP_FIND && p->t.fixed_len > 65535) return NEEDLE_OK; // (the kernel's slot key holds a match length in 16 bits)
+        if (op == OP_FIND && p->t.fixed_len > 65535) return NEEDLE_OK;
         if (!ngram_packed_lds_bytes(tp->prog.hdr, tp->prog.ng.p) || !ngram_watch_allows(p, tp)) return NEEDLE_OK;
-        ScanArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.rows = (const uint8_t *)v->data;
-        sa.n_rows = v->n_rows;
-        sa.prog = tp->d_blob;
-        sa.hdr = tp->prog.hdr;
-        sa.fixed_len = op == OP_FIND ? p->t.fixed_len : -1;
-        sa.bitmap = d_bitmap;
-        sa.start = d_start;
-        sa.end = d_end;
-        sa.packed = op == OP_FIND ? d_packed : nullptr;
-        sa.packed8 = packed8 ? 1u : 0u;
-        HIP_TRY(launch_ngram_packed(op, sa, v->offsets, d_overflow, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, n_cus, (hipStream_t)stream, cw, page, sub));
-        HIP_TRY(ngram_watch_after_launch(tp, (hipStream_t)stream));
+        const ScanArgs sa = scan_args(v, tp, nullptr, fixed_len, out);
+        HIP_TRY(launch_ngram_packed(op, sa, v->offsets, d_overflow, tp->prog.ng.p, tp->d_ng, tp->d_ng_stats, c.n_cus, stream, cw, c.page, c.sub));
+        HIP_TRY(ngram_watch_after_launch(tp, stream));
         *launched = true;
         return NEEDLE_OK;
     };
-    bool launched = false;
-    const Utf16Route u16 = cw == 2 ? utf16_route(p) : Utf16Route();
-    if (filter_ok && cw == 2 && u16.page >= 0) { // one-page UTF-16: the page's byte program, narrowed on load
-        const DevProgram *tp = nullptr;
-        filter_route_utf16_page(p, op, which, need_backward, u16, &tp, &n_cus);
-        if (tp) {
-            rc = try_filter(tp, u16.page, u16.sub, &launched);
-            if (rc || launched) return rc;
-        }
-    }
-    rc = get_program(p, which, cw, need_backward ? 2 : 0, &fp, &n_cus);
-    if (rc) return rc;
-    if (filter_ok && cw == 2 && u16.page < 0 && wide_filter_wanted(fp->prog.hdr.mode)) { // multi-page UTF-16: the WIDE filter
-        const DevProgram *tp = nullptr;
-        rc = filter_route_wide(p, op, which, &tp);
-        if (rc) return rc;
-        if (tp) {
-            rc = try_filter(tp, 0, 0, &launched);
-            if (rc || launched) return rc;
-        }
-    }
-    if (filter_ok && cw == 1 && (fp->prog.hdr.mode == MODE_HYBRID || fp->prog.hdr.mode == MODE_GLOBAL)) { // walks out of HBM / L2 (variant 9)
-        const DevProgram *tp = nullptr, *bwp = nullptr;
-        rc = filter_route_hbm(p, op, which, need_backward, false, &tp, &bwp);
-        if (rc) return rc;
-        if (tp) {
-            rc = try_filter(tp, 0, 0xFF, &launched);
-            if (rc || launched) return rc;
-        }
-    }
-    bool lengths_form = false;
-    if (need_backward && find_lengths_for(fp->prog.hdr.mode)) {
-        const DevProgram *lp = nullptr;
-        rc = get_program(p, W_FORWARDS, cw, 7, &lp, nullptr);
-        if (rc) return rc;
-        static const bool force_tables = getenv("NEEDLE_FIND_LENGTHS") && atoi(getenv("NEEDLE_FIND_LENGTHS")) > 1; // (as run_dev)
-        if (lp && fp->prog.hdr.mode == MODE_PAIR && lp->prog.hdr.mode != MODE_PAIR && !force_tables) lp = nullptr;
-        if (lp) fp = lp, lengths_form = true;
-    }
-    // 8-bit rows of an LDS program that carries a filter of its own (fp->d_ng), as run_dev's last route
-    if (filter_ok && cw == 1 && fp->d_ng && fp->prog.ng.p.on && (op == OP_CONTAINED_IN || lengths_form || p->t.fixed_len >= 0)) {
-        rc = try_filter(fp, 0, 0xFF, &launched);
+    Route r;
+    rc = choose_route(p, op, cw, caps, try_filter, [](Route *, bool *) { return (int)NEEDLE_OK; }, &r);
+    if (rc || r.kind != Route::SCAN) return rc;
+    if (r.own_filter) {
+        bool launched = false;
+        rc = try_filter(r, &launched);
         if (rc || launched) return rc;
     }
     PackedArgs a;
     memset(&a, 0, sizeof(a));
-    a.s.rows = (const uint8_t *)v->data;
-    a.s.n_rows = v->n_rows;
-    a.s.prog = fp->d_blob;
-    a.s.hdr = fp->prog.hdr;
-    a.s.fixed_len = -1;
-    if (op == OP_FIND) {
-        a.s.fixed_len = p->t.fixed_len;
-        if (a.s.fixed_len < 0 && !lengths_form) {
-            const DevProgram *bp = nullptr;
-            rc = get_program(p, W_BACKWARDS, cw, 1, &bp, nullptr);
-            if (rc) return rc;
-            a.s.bprog = bp->d_blob;
-            a.s.bhdr = bp->prog.hdr;
-        }
-    }
-    a.s.bitmap = d_bitmap;
-    a.s.start = d_start;
-    a.s.end = d_end;
-    if (op == OP_FIND) {
-        a.s.from = d_from;
-        a.s.packed = d_packed;
-        a.s.packed8 = packed8 ? 1u : 0u;
-        a.overflow = d_packed ? d_overflow : nullptr;
-    }
+    a.s = scan_args(v, r.fp, r.bp, fixed_len, out);
+    a.s.from = d_from;
     a.offsets = v->offsets;
-    HIP_TRY(launch_packed(op, cw, a, n_cus, (hipStream_t)stream));
+    a.overflow = d_packed ? d_overflow : nullptr;
+    HIP_TRY(launch_packed(op, cw, a, r.n_cus, stream));
     return NEEDLE_OK;
 }
 
@@ -1475,21 +1507,13 @@ static bool packed_find_all_takes(const ProgHeader &h, int char_width) {
 // transducer -- the order of needle_pattern_find_all_transducer), or *tp = nullptr: the pattern goes by conversion.
 static int packed_find_all_program(needle_pattern *p, int cw, const DevProgram **tp, int *n_cus) {
     *tp = nullptr;
-    int rc = get_program(p, W_FORWARDS, cw, 8, tp, n_cus);
+    int rc = get_program(p, W_FORWARDS, cw, V_FA_TRANSDUCER, tp, n_cus);
     if (rc) return rc;
     if (!*tp && p->t.fixed_len < 0) {
-        rc = get_program(p, W_FORWARDS, cw, 11, tp, n_cus);
+        rc = get_program(p, W_FORWARDS, cw, V_FA_RUNS, tp, n_cus);
         if (rc) return rc;
     }
     if (*tp && !packed_find_all_takes((*tp)->prog.hdr, cw)) *tp = nullptr;
-    return NEEDLE_OK;
-}
-
-static int check_packed_dev(const needle_pattern *p, const needle_packed_view *v) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
     return NEEDLE_OK;
 }
 
@@ -1499,11 +1523,7 @@ static int packed_find_all_launch(const needle_packed_view *v, const DevProgram 
                                   hipStream_t stream) {
     PackedFindAllArgs a;
     memset(&a, 0, sizeof(a));
-    a.f.s.rows = (const uint8_t *)v->data;
-    a.f.s.n_rows = v->n_rows;
-    a.f.s.prog = tp->d_blob;
-    a.f.s.hdr = tp->prog.hdr;
-    a.f.s.fixed_len = -1;
+    a.f.s = scan_args(v, tp, nullptr, -1, ScanOut());
     a.f.counts = d_counts;
     a.f.offsets = d_offsets;
     a.f.starts = d_start;
@@ -1655,13 +1675,12 @@ int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_
 // [r0, r1), at least `align` rows (or the rest), grown `align` rows at a time while the chunk's text + per_row bytes per row stay within
 // NEEDLE_HOST_CHUNK_BYTES.
 static std::vector<std::pair<uint64_t, uint64_t>> packed_host_chunks(const needle_packed_view *v, uint64_t per_row, uint64_t align) {
-    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
     const uint64_t n = v->n_rows, cw = v->char_width;
     auto cost = [&](uint64_t r0, uint64_t r1) { return (v->offsets[r1] - v->offsets[r0]) * cw + (r1 - r0) * per_row; };
     std::vector<std::pair<uint64_t, uint64_t>> chunks;
     for (uint64_t r0 = 0; r0 < n;) {
         uint64_t r1 = std::min<uint64_t>(r0 + align, n);
-        while (r1 < n && cost(r0, std::min<uint64_t>(r1 + align, n)) <= kHostChunkBytes) r1 = std::min<uint64_t>(r1 + align, n);
+        while (r1 < n && cost(r0, std::min<uint64_t>(r1 + align, n)) <= host_chunk_bytes()) r1 = std::min<uint64_t>(r1 + align, n);
         chunks.emplace_back(r0, r1);
         r0 = r1;
     }
@@ -1702,66 +1721,38 @@ int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed
     *total = 0;
     const uint64_t n = v->n_rows, cw = v->char_width;
     if (n == 0) return NEEDLE_OK;
-    for (uint64_t r = 0; r < n; ++r)
-        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
+    uint64_t max_len = 0;
+    if ((rc = check_packed_host_offsets(v, &max_len))) return rc;
     if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    static const uint64_t kResultBytes = getenv("NEEDLE_HOST_RESULT_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_RESULT_BYTES")) : (512ull << 20);
-    const uint64_t max_m = std::max<uint64_t>(kResultBytes / 8, 1);
     auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
     std::vector<uint64_t> local;
     std::vector<uint32_t> counts;
     for (const auto &chunk : packed_host_chunks(v, 12, 1)) { // (12 bytes per row: offset + count)
         const uint64_t r0 = chunk.first, r1 = chunk.second, nr = r1 - r0, text = (v->offsets[r1] - v->offsets[r0]) * cw;
-        uint8_t *d = nullptr, *d_out = nullptr; // data | offsets | counts | CSR offsets;  start | end
+        DevAllocs dev;
+        uint8_t *d = nullptr; // data | offsets | counts | CSR offsets
         const uint64_t o_off = up16(std::max<uint64_t>(text, 4)), o_cnt = o_off + up16((nr + 1) * 8), o_csr = o_cnt + up16(nr * 4),
                        all = o_csr + up16((nr + 1) * 8);
-        HIP_TRY(hipMalloc((void **)&d, all));
-        auto done = [&](int code) {
-            (void)hipFree(d);
-            if (d_out) (void)hipFree(d_out);
-            return code;
-        };
+        HIP_TRY(dev.alloc(&d, all));
         needle_packed_view dv;
         hipError_t e = upload_packed_chunk(v, r0, r1, d, (uint64_t *)(d + o_off), local, &dv);
-        if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host upload"));
+        if (e != hipSuccess) return hip_fail(e, "find_all_csr_packed_host upload");
         rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(d + o_cnt), nullptr);
-        if (rc) return done(rc);
+        if (rc) return rc;
         counts.resize(nr);
         e = hipMemcpy(counts.data(), d + o_cnt, nr * 4, hipMemcpyDeviceToHost); // (synchronises with the count pass)
-        if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host counts"));
+        if (e != hipSuccess) return hip_fail(e, "find_all_csr_packed_host counts");
         for (uint64_t r = 0; r < nr; ++r) offsets[r0 + r + 1] = offsets[r0 + r] + counts[r];
         if (offsets[r1] > offsets[r0] && offsets[r1] <= capacity) {
-            uint64_t biggest = 0; // the fill pass in sub-ranges: at least one row, at most max_m matches (one row may exceed it)
-            std::vector<std::pair<uint64_t, uint64_t>> ranges;
-            for (uint64_t a = r0; a < r1;) {
-                uint64_t b = a + 1;
-                while (b < r1 && offsets[b + 1] - offsets[a] <= max_m) ++b;
-                ranges.emplace_back(a, b);
-                biggest = std::max<uint64_t>(biggest, offsets[b] - offsets[a]);
-                a = b;
-            }
-            e = hipMalloc((void **)&d_out, 2 * up16(biggest * 4) + 16);
-            if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host results"));
-            for (const auto &rg : ranges) {
-                const uint64_t a = rg.first, sn = rg.second - rg.first, m = offsets[rg.second] - offsets[a];
-                if (m == 0) continue;
-                local.resize(sn + 1);
-                for (uint64_t r = 0; r <= sn; ++r) local[r] = offsets[a + r] - offsets[a];
-                e = hipMemcpy(d + o_csr, local.data(), (sn + 1) * 8, hipMemcpyHostToDevice);
-                if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host offsets"));
-                needle_packed_view sv = dv;
-                sv.offsets = dv.offsets + (a - r0);
-                sv.n_rows = sn;
-                int more = 0;
-                rc = needle_find_all_csr_packed_dev(p, &sv, (const uint64_t *)(d + o_csr), (int32_t *)d_out, (int32_t *)(d_out + up16(biggest * 4)), &more, nullptr);
-                if (rc) return done(rc);
-                if (more) return done(fail(NEEDLE_ERR_DEVICE, "find_all_csr_packed_host: count pass and fill pass disagree"));
-                e = hipMemcpy(start + offsets[a], d_out, m * 4, hipMemcpyDeviceToHost);
-                if (e == hipSuccess) e = hipMemcpy(end + offsets[a], d_out + up16(biggest * 4), m * 4, hipMemcpyDeviceToHost);
-                if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_packed_host download"));
-            }
+            rc = csr_fill_pass("find_all_csr_packed_host", offsets, r0, r1, d + o_csr, start, end, dev,
+                               [&](uint64_t a, uint64_t sn, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
+                                   needle_packed_view sv = dv;
+                                   sv.offsets = dv.offsets + (a - r0);
+                                   sv.n_rows = sn;
+                                   return needle_find_all_csr_packed_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
+                               });
+            if (rc) return rc;
         }
-        done(NEEDLE_OK);
     }
     *total = offsets[n];
     return NEEDLE_OK;
@@ -1798,31 +1789,22 @@ static int run_packed_compact_host(const needle_pattern *p, const needle_packed_
     // data | offsets | bitmap | results (one buffer for every chunk)
     const uint64_t o_off = biggest, o_bm = o_off + up16((max_rows + 1) * 8), o_res = o_bm + up16(((max_rows + 63) / 64) * 8),
                    all = o_res + up16(max_rows * rb);
+    DevAllocs dev;
     uint8_t *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, all));
+    HIP_TRY(dev.alloc(&d, all));
     std::vector<uint64_t> local;
     for (const auto &c : chunks) {
         const uint64_t r0 = c.first, nr = c.second - c.first;
         needle_packed_view dv;
         hipError_t e = upload_packed_chunk(v, r0, c.second, d, (uint64_t *)(d + o_off), local, &dv);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return hip_fail(e, "find_packed_packed_host upload");
-        }
+        if (e != hipSuccess) return hip_fail(e, "find_packed_packed_host upload");
         rc = packed8 ? needle_find_packed8_packed_dev(p, &dv, (uint64_t *)(d + o_bm), (uint16_t *)(d + o_res), nullptr, nullptr)
                      : needle_find_packed16_packed_dev(p, &dv, (uint64_t *)(d + o_bm), (uint32_t *)(d + o_res), nullptr, nullptr);
-        if (rc) {
-            (void)hipFree(d);
-            return rc;
-        }
+        if (rc) return rc;
         e = hipMemcpy(bitmap + r0 / 64, d + o_bm, ((nr + 63) / 64) * 8, hipMemcpyDeviceToHost); // (synchronises with the scan)
         if (e == hipSuccess) e = hipMemcpy((uint8_t *)out + r0 * rb, d + o_res, nr * rb, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return hip_fail(e, "find_packed_packed_host download");
-        }
+        if (e != hipSuccess) return hip_fail(e, "find_packed_packed_host download");
     }
-    (void)hipFree(d);
     return NEEDLE_OK;
 }
 
@@ -1992,12 +1974,10 @@ int needle_pattern_program_info(const needle_pattern *p, int which, int char_wid
     memset(o, 0, sizeof(*o));
     const bool backward = with_backward != 0 && which == W_FORWARDS && p->t.fixed_len < 0;
     Program pr = lower(p->t, (Which)which, char_width, max_prog_lds(), false, backward);
-    if (backward && find_lengths_for(pr.hdr.mode)) { // (as run_dev chooses)
+    if (backward && find_lengths_for(pr.hdr.mode)) { // (choose_route, route 5)
         if (const MatchLengths *ml = pattern_ml(p)) {
             Program lp = lower_match_lengths(p->t, *ml, char_width, max_prog_lds(), false);
-            static const bool force_tables = getenv("NEEDLE_FIND_LENGTHS") && atoi(getenv("NEEDLE_FIND_LENGTHS")) > 1;
-            const bool pair_lost = pr.hdr.mode == MODE_PAIR && lp.hdr.mode != MODE_PAIR && !force_tables;
-            if (!lp.blob.empty() && !pair_lost) pr = std::move(lp), o->lengths_form = 1;
+            if (!lp.blob.empty() && takes_lengths_form(pr.hdr.mode, lp.hdr.mode)) pr = std::move(lp), o->lengths_form = 1;
         }
     }
     o->mode = (int32_t)pr.hdr.mode;
@@ -2020,9 +2000,62 @@ int needle_pattern_program_info(const needle_pattern *p, int which, int char_wid
 }
 
 // The n-gram candidate filter (needle_ngram_host.h) of the program containedIn() (which = 1) / find() (which = 2) runs on 8-bit
-// rows, as run_dev chooses it: whether there is one, its parameters, why not, and (bitmap != NULL) the bitmap itself.
+// rows, as choose_route chooses it: whether there is one, its parameters, why not, and (bitmap != NULL) the bitmap itself.
 static int prefilter_info_uncached(const needle_pattern *p, int which, needle_prefilter_info *o, std::vector<uint32_t> *bitmap_out, bool wide,
-                                   uint32_t *m1b, uint32_t *m2b);
+                                   uint32_t *m1b, uint32_t *m2b) {
+    memset(o, 0, sizeof(*o));
+    *m1b = *m2b = 0;
+    const bool backward = which == W_FORWARDS && p->t.fixed_len < 0;
+    Program pr;
+    bool usable = which == W_CONTAINED_IN || p->t.fixed_len >= 0;
+    if (wide) { // (as run_dev / find_all_one_pass build it; whether a batch takes it also depends on the ordinary UTF-16 program's mode)
+        const MatchLengths *ml = backward ? pattern_ml(p) : nullptr;
+        if (p->t.class_map.size() == 65536 && (!backward || ml)) pr = lower_filter_wide(p->t, (Which)which, ml), usable = true;
+        else memset(&pr.hdr, 0, sizeof(pr.hdr)), memset(&pr.ng.p, 0, sizeof(pr.ng.p)), pr.hdr.mode = MODE_GLOBAL;
+    } else
+    pr = lower(p->t, (Which)which, 1, max_prog_lds(), false, backward);
+    if (!wide && backward && find_lengths_for(pr.hdr.mode)) {
+        if (const MatchLengths *ml = pattern_ml(p)) {
+            Program lp = lower_match_lengths(p->t, *ml, 1, max_prog_lds(), false);
+            if (!lp.blob.empty() && takes_lengths_form(pr.hdr.mode, lp.hdr.mode)) pr = std::move(lp), usable = true;
+        }
+    }
+    if (!wide && (pr.hdr.mode == MODE_HYBRID || pr.hdr.mode == MODE_GLOBAL) && ngram_level() > 0) {
+        // an automaton that fits the LDS in no form: the filter program walks its table out of HBM / L2 (lower_filter_hbm)
+        const MatchLengths *ml = backward ? pattern_ml(p) : nullptr;
+        if (!backward || ml) {
+            Program hp = lower_filter_hbm(p->t, (Which)which, ml);
+            if (!hp.blob.empty() && hp.hdr.mode == MODE_GLOBAL) pr = std::move(hp), usable = true;
+        } else if (prefilter_unbounded_on()) { // no bounded match lengths: the forward search automaton + backward walks (V_FILTER_UNBOUNDED)
+            Program hp = lower_filter_hbm(p->t, (Which)which, nullptr, true);
+            if (!hp.blob.empty() && hp.hdr.mode == MODE_GLOBAL) pr = std::move(hp), usable = true;
+        }
+    }
+    // (find() of a pattern without bounded match lengths: behind the filter of its ordinary LDS-resident program, starts by backward walks)
+    if (!wide && !usable && backward && prefilter_unbounded_on() && pr.hdr.mode != MODE_GLOBAL && pr.hdr.mode != MODE_HYBRID) usable = true;
+    const NgramFilter &f = pr.ng;
+    o->mode = (int32_t)pr.hdr.mode;
+    if (!usable) {
+        snprintf(o->why, sizeof(o->why), "find() needs its backward walk for this pattern");
+        return NEEDLE_OK;
+    }
+    o->on = (int32_t)(f.p.on && ngram_lds_bytes(pr.hdr, f.p) ? 1 : 0);
+    o->stride = (int32_t)f.p.stride;
+    o->warm = (int32_t)f.p.warm;
+    o->min_len = (int32_t)f.p.min_len;
+    o->n_windows = (int32_t)f.p.n_grams;
+    o->bitmap_bytes = (int32_t)f.p.bm_bytes;
+    o->m1 = f.p.m1, o->m2 = f.p.m2, o->addr_shift = f.p.addr_shift, o->addr_mask = f.p.addr_mask;
+    *m1b = f.p.m1b, *m2b = f.p.m2b;
+    o->on2 = (int32_t)(o->on ? f.p.on2 : 0); // (2: two-sided, NgramParams::on2)
+    if (o->on2) o->n_windows2 = (int32_t)f.p.n_grams2, o->bitmap2_bytes = (int32_t)f.p.bm2_bytes, o->m3 = f.p.m3, o->addr_mask2 = f.p.addr_mask2;
+    snprintf(o->why, sizeof(o->why), "%s", f.p.on ? "" : (f.why.empty() ? (ngram_level() > 0 ? "not a mode the filter is built for" : "NEEDLE_PREFILTER=0") : f.why.c_str()));
+    if (f.p.on) {
+        *bitmap_out = f.bitmap;
+        if (o->on2) bitmap_out->insert(bitmap_out->end(), f.bitmap2.begin(), f.bitmap2.end()); // (the second level's right behind)
+    }
+    return NEEDLE_OK;
+}
 
 // wide: the filter of UTF-16 rows of a pattern on several pages of the BMP (lower_filter_wide).  At most cap_words bitmap words are written.
 int needle_pattern_prefilter_info2(const needle_pattern *cp, int which, int wide, needle_prefilter_info2 *o, uint32_t *bitmap, size_t cap_words) {
@@ -2095,66 +2128,6 @@ int needle_pattern_prefilter_state(const needle_pattern *cp, int which, needle_p
         o->last_candidates_per_kib = dp.ng_last_rate;
         o->filter_launches = dp.ng_launches;
         o->suspended_calls = dp.ng_suspended_calls;
-    }
-    return NEEDLE_OK;
-}
-
-static int prefilter_info_uncached(const needle_pattern *p, int which, needle_prefilter_info *o, std::vector<uint32_t> *bitmap_out, bool wide,
-                                   uint32_t *m1b, uint32_t *m2b) {
-    memset(o, 0, sizeof(*o));
-    *m1b = *m2b = 0;
-    const bool backward = which == W_FORWARDS && p->t.fixed_len < 0;
-    Program pr;
-    bool usable = which == W_CONTAINED_IN || p->t.fixed_len >= 0;
-    if (wide) { // (as run_dev / find_all_one_pass build it; whether a batch takes it also depends on the ordinary UTF-16 program's mode)
-        const MatchLengths *ml = backward ? pattern_ml(p) : nullptr;
-        if (p->t.class_map.size() == 65536 && (!backward || ml)) pr = lower_filter_wide(p->t, (Which)which, ml), usable = true;
-        else memset(&pr.hdr, 0, sizeof(pr.hdr)), memset(&pr.ng.p, 0, sizeof(pr.ng.p)), pr.hdr.mode = MODE_GLOBAL;
-    } else
-    pr = lower(p->t, (Which)which, 1, max_prog_lds(), false, backward);
-    if (!wide && backward && find_lengths_for(pr.hdr.mode)) {
-        if (const MatchLengths *ml = pattern_ml(p)) {
-            Program lp = lower_match_lengths(p->t, *ml, 1, max_prog_lds(), false);
-            static const bool force_tables = getenv("NEEDLE_FIND_LENGTHS") && atoi(getenv("NEEDLE_FIND_LENGTHS")) > 1;
-            const bool pair_lost = pr.hdr.mode == MODE_PAIR && lp.hdr.mode != MODE_PAIR && !force_tables;
-            if (!lp.blob.empty() && !pair_lost) pr = std::move(lp), usable = true;
-        }
-    }
-    if (!wide && (pr.hdr.mode == MODE_HYBRID || pr.hdr.mode == MODE_GLOBAL) && ngram_level() > 0) {
-        // an automaton that fits the LDS in no form: the filter program walks its table out of HBM / L2 (lower_filter_hbm)
-        const MatchLengths *ml = backward ? pattern_ml(p) : nullptr;
-        static const bool unbounded_hbm = !(getenv("NEEDLE_PREFILTER_UNBOUNDED") && atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) == 0);
-        if (!backward || ml) {
-            Program hp = lower_filter_hbm(p->t, (Which)which, ml);
-            if (!hp.blob.empty() && hp.hdr.mode == MODE_GLOBAL) pr = std::move(hp), usable = true;
-        } else if (unbounded_hbm) { // no bounded match lengths: the forward search automaton + backward walks (get_program variant 12)
-            Program hp = lower_filter_hbm(p->t, (Which)which, nullptr, true);
-            if (!hp.blob.empty() && hp.hdr.mode == MODE_GLOBAL) pr = std::move(hp), usable = true;
-        }
-    }
-    // (find() of a pattern without bounded match lengths: behind the filter of its ordinary LDS-resident program, starts by backward walks)
-    static const bool unbounded_on = !(getenv("NEEDLE_PREFILTER_UNBOUNDED") && atoi(getenv("NEEDLE_PREFILTER_UNBOUNDED")) == 0);
-    if (!wide && !usable && backward && unbounded_on && pr.hdr.mode != MODE_GLOBAL && pr.hdr.mode != MODE_HYBRID) usable = true;
-    const NgramFilter &f = pr.ng;
-    o->mode = (int32_t)pr.hdr.mode;
-    if (!usable) {
-        snprintf(o->why, sizeof(o->why), "find() needs its backward walk for this pattern");
-        return NEEDLE_OK;
-    }
-    o->on = (int32_t)(f.p.on && ngram_lds_bytes(pr.hdr, f.p) ? 1 : 0);
-    o->stride = (int32_t)f.p.stride;
-    o->warm = (int32_t)f.p.warm;
-    o->min_len = (int32_t)f.p.min_len;
-    o->n_windows = (int32_t)f.p.n_grams;
-    o->bitmap_bytes = (int32_t)f.p.bm_bytes;
-    o->m1 = f.p.m1, o->m2 = f.p.m2, o->addr_shift = f.p.addr_shift, o->addr_mask = f.p.addr_mask;
-    *m1b = f.p.m1b, *m2b = f.p.m2b;
-    o->on2 = (int32_t)(o->on ? f.p.on2 : 0); // (2: two-sided, NgramParams::on2)
-    if (o->on2) o->n_windows2 = (int32_t)f.p.n_grams2, o->bitmap2_bytes = (int32_t)f.p.bm2_bytes, o->m3 = f.p.m3, o->addr_mask2 = f.p.addr_mask2;
-    snprintf(o->why, sizeof(o->why), "%s", f.p.on ? "" : (f.why.empty() ? (ngram_level() > 0 ? "not a mode the filter is built for" : "NEEDLE_PREFILTER=0") : f.why.c_str()));
-    if (f.p.on) {
-        *bitmap_out = f.bitmap;
-        if (o->on2) bitmap_out->insert(bitmap_out->end(), f.bitmap2.begin(), f.bitmap2.end()); // (the second level's right behind)
     }
     return NEEDLE_OK;
 }
@@ -2330,6 +2303,10 @@ int needle_find_next_dev(const needle_pattern *p, const needle_batch_view *v, co
 }
 // The round-per-match form: one needle_find_next pass over the batch per round, one stream synchronisation per round.
 // Rows of 64 MiB and more (stripe paths only) take it; NEEDLE_FIND_ALL_ROUNDS=1 forces it (tests cross-check the two).
+static bool find_all_rounds_forced() {
+    static const bool forced = (getenv("NEEDLE_FIND_ALL_ROUNDS") ? atoi(getenv("NEEDLE_FIND_ALL_ROUNDS")) : 0) != 0;
+    return forced;
+}
 static int find_all_rounds(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *d_counts, int32_t *d_start,
                            int32_t *d_end, int *more, hipStream_t stream) {
     const size_t n = (size_t)v->n_rows, words = (n + 63) / 64;
@@ -2367,9 +2344,11 @@ static int find_all_rounds(const needle_pattern *p, const needle_batch_view *v, 
 
 // One pass over the batch: every row is fetched once, each lane restarts its search where its last match ended
 // (needle_find_all.hip).  Dense slots (offsets == nullptr), compact filing at caller-computed offsets, or counting only.
+// The program is chosen by find-all's own rules (not choose_route's: other programs, other switches); the pieces are the shared ones.
 static int find_all_one_pass(needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *d_counts, int32_t *d_start,
                              int32_t *d_end, const uint64_t *d_offsets, bool count_only, int *more, hipStream_t stream,
                              uint32_t *d_packed = nullptr, uint32_t kshift = 0) {
+    const int cw = (int)v->char_width;
     const uint64_t stride_bytes = v->row_stride * v->char_width;
     if (stride_bytes >= (1ull << 26)) return fail(NEEDLE_ERR_UNSUPPORTED, "rows of 64 MiB or more: only needle_find_all_dev (round per match) takes them");
     const DevProgram *fp = nullptr, *bp = nullptr;
@@ -2378,180 +2357,113 @@ static int find_all_one_pass(needle_pattern *p, const needle_batch_view *v, uint
     int rc = NEEDLE_OK;
     // start = end - (the match length the automaton's end state remembers): no backward walks at all, when the pattern
     // allows it (needle_lower.h: keyword unions and the like).  NEEDLE_FIND_ALL_LENGTHS=0: off (A/B, tests).
-    static const bool lengths_on = !(getenv("NEEDLE_FIND_ALL_LENGTHS") && atoi(getenv("NEEDLE_FIND_ALL_LENGTHS")) == 0);
+    static const int lengths_level = getenv("NEEDLE_FIND_ALL_LENGTHS") ? atoi(getenv("NEEDLE_FIND_ALL_LENGTHS")) : 1;
+    const bool lengths_on = lengths_level != 0;
     bool lmode = false;
     if (need_backward && lengths_on && !count_only) {
-        rc = get_program(p, W_FORWARDS, (int)v->char_width, 6, &fp, &n_cus);
+        rc = get_program(p, W_FORWARDS, cw, V_FA_LENGTHS, &fp, &n_cus);
         if (rc) return rc;
         lmode = fp != nullptr;
-        static const bool sparse_lengths = getenv("NEEDLE_FIND_ALL_LENGTHS") && atoi(getenv("NEEDLE_FIND_ALL_LENGTHS")) > 1;
-        if (!lmode && sparse_lengths && find_lengths_for(MODE_SPARSE)) {
+        if (!lmode && lengths_level > 1 && find_lengths_for(MODE_SPARSE)) {
             // no plain LDS table holds the lengths automaton (a big dictionary): the scan kernels' compressed form of it, if there is
             // one.  Opt-in (NEEDLE_FIND_ALL_LENGTHS=2): measured on C3-sparse (profiles/r04_find_all.md) it is no faster than hot rows +
             // backward walks, 2.05 against 1.98 ms -- the per-lane piece walk is what costs there, not the 0.25 starts per row
             const DevProgram *sp = nullptr;
-            rc = get_program(p, W_FORWARDS, (int)v->char_width, 7, &sp, &n_cus);
+            rc = get_program(p, W_FORWARDS, cw, V_LENGTHS, &sp, &n_cus);
             if (rc) return rc;
             if (sp && sp->prog.hdr.mode == MODE_SPARSE) fp = sp, lmode = true;
         }
         if (lmode) need_backward = false;
     }
+    // the find-all outputs, common to the three kernels below (s: the rows and the program, filled by each)
+    FindAllArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.slots = slots;
+    fa.kshift = kshift;
+    fa.offsets = d_offsets;
+    fa.count_only = count_only ? 1u : 0u;
+    fa.counts = d_counts;
+    fa.starts = d_start;
+    fa.ends = d_end;
+    fa.packed = d_packed;
     // Dictionaries whose find() runs behind the n-gram candidate filter (needle_ngram.hip): their find-all does too -- the filter
     // kernel's find-all form files every verified candidate and each row sorts its own out against its moving cursor (dense slots,
     // the counting pass and the compact filing alike).  NEEDLE_FIND_ALL_FILTER=0: off (A/B, tests).
-    static const bool fa_filter = !(getenv("NEEDLE_FIND_ALL_FILTER") && atoi(getenv("NEEDLE_FIND_ALL_FILTER")) == 0);
+    static const bool fa_filter = (getenv("NEEDLE_FIND_ALL_FILTER") ? atoi(getenv("NEEDLE_FIND_ALL_FILTER")) : 1) != 0;
     // (UTF-16 rows of a pattern on one page of the BMP: that page's byte programs, the text narrowed as it is loaded -- utf16_route)
-    const Utf16Route u16 = v->char_width == 2 ? utf16_route(p) : Utf16Route();
+    const Utf16Route u16 = cw == 2 ? utf16_route(p) : Utf16Route();
     if (fa_filter && (count_only || d_offsets || slots) && ngram_level() > 0 && (p->t.fixed_len >= 0 || find_lengths_for(MODE_SPARSE))) {
         const DevProgram *sp = nullptr;
         int cus = 0;
-        if (v->char_width == 2 && u16.page < 0) { // several pages of the BMP: the WIDE filter, where find() would take it (run_dev)
+        if (cw == 2 && u16.page < 0) { // several pages of the BMP: the WIDE filter, where find() would take it (choose_route, route 3)
             const DevProgram *op16 = nullptr;
-            rc = get_program(p, W_FORWARDS, 2, p->t.fixed_len < 0 ? 2 : 0, &op16, &cus);
+            rc = get_program(p, W_FORWARDS, 2, p->t.fixed_len < 0 ? V_BACKMAPS : V_PLAIN, &op16, &cus);
             if (rc) return rc;
             if (op16 && wide_filter_wanted(op16->prog.hdr.mode)) {
-                rc = get_program(p, W_FORWARDS, 2, 10, &sp, &cus);
+                rc = get_program(p, W_FORWARDS, 2, V_FILTER_WIDE, &sp, &cus);
                 if (rc) return rc;
             }
         } else {
-        const int cw8 = 1 | ((v->char_width == 2 ? u16.page : 0) << 8);
-        rc = get_program(p, W_FORWARDS, cw8, p->t.fixed_len >= 0 ? 0 : 7, &sp, &cus);
-        if (rc) return rc;
-        if (!(sp && sp->d_ng && sp->prog.ng.p.on)) { // an automaton that fits the LDS in no form: the filter with its walks out of HBM / L2
-            rc = get_program(p, W_FORWARDS, cw8, 9, &sp, &cus);
+            const int cw8 = 1 | ((cw == 2 ? u16.page : 0) << 8);
+            rc = get_program(p, W_FORWARDS, cw8, p->t.fixed_len >= 0 ? V_PLAIN : V_LENGTHS, &sp, &cus);
             if (rc) return rc;
-        }
+            if (!(sp && sp->d_ng && sp->prog.ng.p.on)) { // an automaton that fits the LDS in no form: the filter with its walks out of HBM / L2
+                rc = get_program(p, W_FORWARDS, cw8, V_FILTER_HBM, &sp, &cus);
+                if (rc) return rc;
+            }
         }
         if (sp && sp->d_ng && sp->prog.ng.p.on && ngram_find_all_lds_bytes(sp->prog.hdr, sp->prog.ng.p)) {
             // (UTF-16 rows: the stride in CHARS -- launch_ngram_find_all with char_width 2)
-            const ScanArgs a = filter_scan_args(v, v->row_stride, sp, p->t.fixed_len, nullptr, nullptr, nullptr, nullptr);
-            if (ngram_shape_ok(a) && ngram_watch_allows(p, sp)) {
-                int32_t *d_more = nullptr;
-                HIP_TRY(scratch_malloc((void **)&d_more, 16, stream));
-                hipError_t e = hipMemsetAsync(d_more, 0, 4, stream);
-                if (e == hipSuccess) e = launch_ngram_find_all(a, sp->prog.ng.p, sp->d_ng, sp->d_ng_stats, slots, d_counts, d_start, d_end, d_packed, d_more, d_offsets, count_only, cus, stream, (int)v->char_width, u16.page > 0 ? u16.page : 0, v->char_width == 2 ? u16.sub : 0xFF, kshift);
-                if (e == hipSuccess) e = ngram_watch_after_launch(sp, stream);
-                int32_t m = 0;
-                if (e == hipSuccess && more) {
-                    e = hipMemcpyAsync(&m, d_more, 4, hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                }
-                (void)scratch_free(d_more, stream);
-                if (e != hipSuccess) return hip_fail(e, "find_all (filter kernel)");
-                if (more) *more = m != 0;
-                return NEEDLE_OK;
-            }
+            const ScanArgs a = scan_args(v, v->row_stride, sp, nullptr, p->t.fixed_len, ScanOut());
+            if (ngram_shape_ok(a) && ngram_watch_allows(p, sp))
+                return with_more_flag(stream, more, "find_all (filter kernel)", [&](int32_t *d_more) {
+                    hipError_t e = launch_ngram_find_all(a, sp->prog.ng.p, sp->d_ng, sp->d_ng_stats, slots, d_counts, d_start, d_end, d_packed, d_more, d_offsets,
+                                                         count_only, cus, stream, cw, u16.page > 0 ? u16.page : 0, cw == 2 ? u16.sub : 0xFF, kshift);
+                    if (e == hipSuccess) e = ngram_watch_after_launch(sp, stream);
+                    return e;
+                });
         }
     }
     // Patterns with a find-all transducer (needle_lower.h: bounded match lengths, no match inside a longer live one) are walked in
     // LOCK-STEP: one table lookup per char, every lane at the same char, the restarts folded into the automaton (needle_find_all_ls.hip).
     // NEEDLE_FIND_ALL_LOCKSTEP=0: off (A/B, tests: the per-lane one-pass kernel below).
-    static const bool lockstep_on = !(getenv("NEEDLE_FIND_ALL_LOCKSTEP") && atoi(getenv("NEEDLE_FIND_ALL_LOCKSTEP")) == 0);
-    FindAllArgs shape; // (what the launcher's own check looks at: one definition of "the lock-step kernel takes this shape")
-    memset(&shape, 0, sizeof(shape));
-    shape.slots = slots, shape.s.stride_bytes = stride_bytes;
-    if (lockstep_on && find_all_lockstep_shape_ok(shape)) {
+    static const bool lockstep_on = (getenv("NEEDLE_FIND_ALL_LOCKSTEP") ? atoi(getenv("NEEDLE_FIND_ALL_LOCKSTEP")) : 1) != 0;
+    fa.s.stride_bytes = stride_bytes; // (what the launcher's own check looks at: one definition of "the lock-step kernel takes this shape")
+    if (lockstep_on && find_all_lockstep_shape_ok(fa)) {
         const DevProgram *tp = nullptr;
         int cus = 0;
         if (lengths_on) {
-            rc = get_program(p, W_FORWARDS, (int)v->char_width, 8, &tp, &cus);
+            rc = get_program(p, W_FORWARDS, cw, V_FA_TRANSDUCER, &tp, &cus);
             if (rc) return rc;
         }
         // ... or, without bounded match lengths, the RUN transducer (`[0-9]+`, `[a-z]{3}[a-z]*`: starts from a per-lane run-start register)
-        static const bool runs_on = !(getenv("NEEDLE_FIND_ALL_RUNS") && atoi(getenv("NEEDLE_FIND_ALL_RUNS")) == 0);
+        static const bool runs_on = (getenv("NEEDLE_FIND_ALL_RUNS") ? atoi(getenv("NEEDLE_FIND_ALL_RUNS")) : 1) != 0;
         if (!tp && runs_on && p->t.fixed_len < 0) {
-            rc = get_program(p, W_FORWARDS, (int)v->char_width, 11, &tp, &cus);
+            rc = get_program(p, W_FORWARDS, cw, V_FA_RUNS, &tp, &cus);
             if (rc) return rc;
         }
         if (tp) {
-            FindAllArgs fl;
-            memset(&fl, 0, sizeof(fl));
-            fl.s.rows = (const uint8_t *)v->rows;
-            fl.s.n_rows = v->n_rows;
-            fl.s.stride_bytes = stride_bytes;
-            fl.s.total_bytes = fl.s.n_rows * fl.s.stride_bytes;
-            fl.s.row_len = v->row_len;
-            fl.s.lengths = v->lengths;
-            fl.s.prog = tp->d_blob;
-            fl.s.hdr = tp->prog.hdr;
-            fl.s.fixed_len = -1;
-            fl.slots = slots;
-            fl.kshift = kshift;
-            fl.offsets = d_offsets;
-            fl.count_only = count_only ? 1u : 0u;
-            fl.counts = d_counts;
-            fl.starts = d_start;
-            fl.ends = d_end;
-            fl.packed = d_packed;
-            int32_t *d_more = nullptr;
-            HIP_TRY(scratch_malloc((void **)&d_more, 16, stream));
-            hipError_t e = hipMemsetAsync(d_more, 0, 4, stream);
-            fl.more = d_more;
-            if (e == hipSuccess) e = launch_find_all_lockstep((int)v->char_width, fl, cus, stream);
-            int32_t m = 0;
-            if (e == hipSuccess && more) { // the only synchronisation: the caller asked whether its slots sufficed
-                e = hipMemcpyAsync(&m, d_more, 4, hipMemcpyDeviceToHost, stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            }
-            (void)scratch_free(d_more, stream);
-            if (e != hipSuccess) return hip_fail(e, "find_all (lock-step kernel)");
-            if (more) *more = m != 0;
-            return NEEDLE_OK;
+            fa.s = scan_args(v, stride_bytes, tp, nullptr, -1, ScanOut());
+            return with_more_flag(stream, more, "find_all (lock-step kernel)", [&](int32_t *d_more) {
+                fa.more = d_more;
+                return launch_find_all_lockstep(cw, fa, cus, stream);
+            });
         }
     }
-    if (!lmode) rc = get_program(p, W_FORWARDS, (int)v->char_width, need_backward ? 5 : 4, &fp, &n_cus);
+    if (!lmode) rc = get_program(p, W_FORWARDS, cw, need_backward ? V_FA_BACKMAPS : V_FA_PLAIN, &fp, &n_cus);
     if (rc) return rc;
-    FindAllArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    ScanArgs &a = fa.s;
-    a.rows = (const uint8_t *)v->rows;
-    a.n_rows = v->n_rows;
-    a.stride_bytes = stride_bytes;
-    a.total_bytes = a.n_rows * a.stride_bytes;
-    a.row_len = v->row_len;
-    a.lengths = v->lengths;
-    a.prog = fp->d_blob;
-    a.hdr = fp->prog.hdr;
-    a.fixed_len = p->t.fixed_len;
+    if (need_backward && (rc = backward_program(p, cw, &bp))) return rc;
+    fa.s = scan_args(v, stride_bytes, fp, bp, p->t.fixed_len, ScanOut());
     fa.lmode = lmode ? 1u : 0u;
-    if (need_backward) {
-        rc = get_program(p, W_BACKWARDS, (int)v->char_width, 1, &bp, nullptr);
-        if (rc) return rc;
-        a.bprog = bp->d_blob;
-        a.bhdr = bp->prog.hdr;
-    }
-    fa.slots = slots;
-    fa.kshift = kshift;
-    fa.offsets = d_offsets;
-    fa.count_only = count_only ? 1u : 0u;
-    static const bool no_defer = getenv("NEEDLE_FIND_ALL_DEFER") && atoi(getenv("NEEDLE_FIND_ALL_DEFER")) == 0; // A/B, tests
-    fa.defer = (a.fixed_len < 0 && !a.hdr.root_accepting && !no_defer && !lmode) ? 1u : 0u;
+    static const bool no_defer = (getenv("NEEDLE_FIND_ALL_DEFER") ? atoi(getenv("NEEDLE_FIND_ALL_DEFER")) : 1) == 0; // A/B, tests
+    fa.defer = (fa.s.fixed_len < 0 && !fa.s.hdr.root_accepting && !no_defer && !lmode) ? 1u : 0u;
 #ifdef NEEDLE_TUNING // measurement builds only: start = the search cursor (wrong answers; never in the shipping library)
-    static const bool dbg_no_backward = getenv("NEEDLE_DEBUG_NO_BACKWARD") != nullptr;
-    if (fa.defer && dbg_no_backward) fa.defer = 2;
+    if (fa.defer && debug_no_backward()) fa.defer = 2;
 #endif
-    fa.counts = d_counts;
-    fa.starts = d_start;
-    fa.ends = d_end;
-    fa.packed = d_packed;
-    int32_t *d_more = nullptr;
-    HIP_TRY(scratch_malloc((void **)&d_more, 16, stream));
-    auto done = [&](int code) {
-        (void)scratch_free(d_more, stream);
-        return code;
-    };
-    if (hipMemsetAsync(d_more, 0, 4, stream) != hipSuccess) return done(fail(NEEDLE_ERR_DEVICE, "hipMemsetAsync"));
-    fa.more = d_more;
-    hipError_t e = launch_find_all((int)v->char_width, fa, n_cus, stream);
-    if (e != hipSuccess) return done(hip_fail(e, "find_all"));
-    if (more) { // the only synchronisation: the caller asked whether its slots sufficed
-        int32_t m = 0;
-        e = hipMemcpyAsync(&m, d_more, 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return done(hip_fail(e, "find_all"));
-        *more = m != 0;
-    }
-    return done(NEEDLE_OK);
+    return with_more_flag(stream, more, "find_all", [&](int32_t *d_more) {
+        fa.more = d_more;
+        return launch_find_all(cw, fa, n_cus, stream);
+    });
 }
 
 int needle_find_all_dev(const needle_pattern *cp, const needle_batch_view *v, uint32_t slots, uint32_t *d_counts, int32_t *d_start,
@@ -2564,8 +2476,7 @@ int needle_find_all_dev(const needle_pattern *cp, const needle_batch_view *v, ui
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!d_counts || (slots && (!d_start || !d_end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
     hipStream_t stream = (hipStream_t)stream_;
-    static const bool rounds = getenv("NEEDLE_FIND_ALL_ROUNDS") && atoi(getenv("NEEDLE_FIND_ALL_ROUNDS")) != 0;
-    if (rounds || v->row_stride * v->char_width >= (1ull << 26)) return find_all_rounds(p, v, slots, d_counts, d_start, d_end, more, stream);
+    if (find_all_rounds_forced() || v->row_stride * v->char_width >= (1ull << 26)) return find_all_rounds(p, v, slots, d_counts, d_start, d_end, more, stream);
     return find_all_one_pass(p, v, slots, d_counts, d_start, d_end, nullptr, false, more, stream);
 }
 
@@ -2622,41 +2533,25 @@ int needle_find_all_csr_dev(const needle_pattern *cp, const needle_batch_view *v
 // start_end16 != nullptr: the one-dword-per-match form (needle_find_all_packed16_dev) -- start / end are not used
 static int find_all_host_one(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts, int32_t *start,
                              int32_t *end, int *more, uint32_t *start_end16 = nullptr) {
-    const size_t cw = v->char_width, n = (size_t)v->n_rows;
-    const size_t src_stride = (size_t)v->row_stride * cw;
-    size_t dst_stride = (src_stride + 15) & ~(size_t)15;
-    if (dst_stride == 0) dst_stride = 16;
+    const size_t n = (size_t)v->n_rows, dst_stride = (size_t)padded_stride_bytes(v);
     uint8_t *d = nullptr; // rows | lengths | counts | start | end
     auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_len = up16(n * dst_stride), o_cnt = o_len + up16(n * 4), o_s = o_cnt + up16(n * 4);
     const size_t o_e = o_s + up16(n * slots * 4), total = o_e + (start_end16 ? 0 : up16(n * slots * 4));
-    HIP_TRY(hipMalloc((void **)&d, total));
-    auto done = [&](int code) {
-        (void)hipFree(d);
-        return code;
-    };
-    hipError_t e = hipSuccess;
-    if (dst_stride == src_stride) {
-        e = hipMemcpy(d, v->rows, n * src_stride, hipMemcpyHostToDevice);
-    } else {
-        e = hipMemset(d, 0, n * dst_stride);
-        if (e == hipSuccess && src_stride) e = hipMemcpy2D(d, dst_stride, v->rows, src_stride, src_stride, n, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && v->lengths) e = hipMemcpy(d + o_len, v->lengths, n * 4, hipMemcpyHostToDevice);
+    DevAllocs dev;
+    HIP_TRY(dev.alloc(&d, total));
+    needle_batch_view dv;
+    hipError_t e = upload_rows(v, d, (uint32_t *)(d + o_len), &dv);
     if (e == hipSuccess && slots) e = hipMemset(d + o_s, 0xFF, total - o_s); // -1 in every slot
-    if (e != hipSuccess) return done(hip_fail(e, "find_all_host upload"));
-    needle_batch_view dv = *v;
-    dv.rows = d;
-    dv.lengths = v->lengths ? (const uint32_t *)(d + o_len) : nullptr;
-    dv.row_stride = dst_stride / cw;
+    if (e != hipSuccess) return hip_fail(e, "find_all_host upload");
     int rc = start_end16 ? needle_find_all_packed16_dev(p, &dv, slots, (uint32_t *)(d + o_cnt), (uint32_t *)(d + o_s), more, nullptr)
                          : needle_find_all_dev(p, &dv, slots, (uint32_t *)(d + o_cnt), (int32_t *)(d + o_s), (int32_t *)(d + o_e), more, nullptr);
-    if (rc) return done(rc);
+    if (rc) return rc;
     e = hipMemcpy(counts, d + o_cnt, n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && slots) e = hipMemcpy(start_end16 ? (void *)start_end16 : (void *)start, d + o_s, n * slots * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && slots && !start_end16) e = hipMemcpy(end, d + o_e, n * slots * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(hip_fail(e, "find_all_host download"));
-    return done(NEEDLE_OK);
+    if (e != hipSuccess) return hip_fail(e, "find_all_host download");
+    return NEEDLE_OK;
 }
 
 // (like the other host entry points: at most ~2 GiB of rows + results resident on the device at a time)
@@ -2664,78 +2559,31 @@ static int find_all_host_one(const needle_pattern *p, const needle_batch_view *v
 // pass while the rows are still resident, download.  offsets: n + 1 entries, offsets[0] given by the caller.
 static int find_all_csr_host_one(const needle_pattern *p, const needle_batch_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
                                  uint64_t capacity) {
-    const size_t cw = v->char_width, n = (size_t)v->n_rows;
-    const size_t src_stride = (size_t)v->row_stride * cw;
-    size_t dst_stride = (src_stride + 15) & ~(size_t)15;
-    if (dst_stride == 0) dst_stride = 16;
-    uint8_t *d = nullptr, *d_out = nullptr; // rows | lengths | counts | offsets;  start | end
+    const size_t n = (size_t)v->n_rows, dst_stride = (size_t)padded_stride_bytes(v);
+    uint8_t *d = nullptr; // rows | lengths | counts | offsets
     auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_len = up16(n * dst_stride), o_cnt = o_len + up16(n * 4), o_off = o_cnt + up16(n * 4), total = o_off + up16((n + 1) * 8);
-    HIP_TRY(hipMalloc((void **)&d, total));
-    auto done = [&](int code) {
-        (void)hipFree(d);
-        if (d_out) (void)hipFree(d_out);
-        return code;
-    };
-    hipError_t e = hipSuccess;
-    if (dst_stride == src_stride) {
-        e = hipMemcpy(d, v->rows, n * src_stride, hipMemcpyHostToDevice);
-    } else {
-        e = hipMemset(d, 0, n * dst_stride);
-        if (e == hipSuccess && src_stride) e = hipMemcpy2D(d, dst_stride, v->rows, src_stride, src_stride, n, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && v->lengths) e = hipMemcpy(d + o_len, v->lengths, n * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_host upload"));
-    needle_batch_view dv = *v;
-    dv.rows = d;
-    dv.lengths = v->lengths ? (const uint32_t *)(d + o_len) : nullptr;
-    dv.row_stride = dst_stride / cw;
+    DevAllocs dev;
+    HIP_TRY(dev.alloc(&d, total));
+    needle_batch_view dv;
+    hipError_t e = upload_rows(v, d, (uint32_t *)(d + o_len), &dv);
+    if (e != hipSuccess) return hip_fail(e, "find_all_csr_host upload");
     int rc = needle_count_matches_dev(p, &dv, (uint32_t *)(d + o_cnt), nullptr);
-    if (rc) return done(rc);
+    if (rc) return rc;
     std::vector<uint32_t> counts(n);
     e = hipMemcpy(counts.data(), d + o_cnt, n * 4, hipMemcpyDeviceToHost); // (synchronises with the count pass)
-    if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_host counts"));
+    if (e != hipSuccess) return hip_fail(e, "find_all_csr_host counts");
     for (size_t r = 0; r < n; ++r) offsets[r + 1] = offsets[r] + counts[r];
     const uint64_t m = offsets[n] - offsets[0];
-    if (m == 0 || offsets[n] > capacity) return done(NEEDLE_OK); // nothing to file, or the caller's buffers are too small
-    // The fill pass runs over sub-ranges of the chunk's rows so that the results resident on the device stay bounded too:
-    // a dense-match batch (a one-char pattern over 256-char rows files ~2 KiB per row) would otherwise ask for several
-    // times the chunk's row bytes in one allocation.  NEEDLE_HOST_RESULT_BYTES: that bound (tests shrink it).
-    static const uint64_t kResultBytes = getenv("NEEDLE_HOST_RESULT_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_RESULT_BYTES")) : (512ull << 20);
-    const uint64_t max_m = std::max<uint64_t>(kResultBytes / 8, 1);
-    std::vector<std::pair<size_t, size_t>> ranges; // [r0, r1): at least one row, at most max_m matches (one row may exceed it)
-    uint64_t biggest = 0;
-    for (size_t r0 = 0; r0 < n;) {
-        size_t r1 = r0 + 1;
-        while (r1 < n && offsets[r1 + 1] - offsets[r0] <= max_m) ++r1;
-        ranges.emplace_back(r0, r1);
-        biggest = std::max<uint64_t>(biggest, offsets[r1] - offsets[r0]);
-        r0 = r1;
-    }
-    e = hipMalloc((void **)&d_out, 2 * up16(biggest * 4) + 16);
-    if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_host results"));
-    std::vector<uint64_t> local;
-    for (const auto &rg : ranges) {
-        const size_t r0 = rg.first, nr = rg.second - rg.first;
-        const uint64_t mr = offsets[rg.second] - offsets[r0];
-        if (mr == 0) continue;
-        local.resize(nr + 1);
-        for (size_t r = 0; r <= nr; ++r) local[r] = offsets[r0 + r] - offsets[r0];
-        e = hipMemcpy(d + o_off, local.data(), (nr + 1) * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_host offsets"));
-        needle_batch_view sv = dv;
-        sv.rows = d + r0 * dst_stride;
-        sv.lengths = dv.lengths ? dv.lengths + r0 : nullptr;
-        sv.n_rows = nr;
-        int more = 0;
-        rc = needle_find_all_csr_dev(p, &sv, (const uint64_t *)(d + o_off), (int32_t *)d_out, (int32_t *)(d_out + up16(biggest * 4)), &more, nullptr);
-        if (rc) return done(rc);
-        if (more) return done(fail(NEEDLE_ERR_DEVICE, "find_all_csr_host: count pass and fill pass disagree"));
-        e = hipMemcpy(start + offsets[r0], d_out, mr * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(end + offsets[r0], d_out + up16(biggest * 4), mr * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return done(hip_fail(e, "find_all_csr_host download"));
-    }
-    return done(NEEDLE_OK);
+    if (m == 0 || offsets[n] > capacity) return NEEDLE_OK; // nothing to file, or the caller's buffers are too small
+    return csr_fill_pass("find_all_csr_host", offsets, 0, n, d + o_off, start, end, dev,
+                         [&](uint64_t r0, uint64_t nr, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
+                             needle_batch_view sv = dv;
+                             sv.rows = d + r0 * dst_stride;
+                             sv.lengths = dv.lengths ? dv.lengths + r0 : nullptr;
+                             sv.n_rows = nr;
+                             return needle_find_all_csr_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
+                         });
 }
 int needle_find_all_csr_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
                              uint64_t capacity, uint64_t *total) {
@@ -2747,19 +2595,9 @@ int needle_find_all_csr_host(const needle_pattern *p, const needle_batch_view *v
     offsets[0] = 0;
     *total = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
-    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
-    const uint64_t row_bytes = std::max<uint64_t>(16, (v->row_stride * v->char_width + 15) & ~(uint64_t)15) + 16;
-    const uint64_t per = std::max<uint64_t>(64, (kHostChunkBytes / row_bytes) & ~(uint64_t)63);
-    for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
-        needle_batch_view c = *v;
-        c.n_rows = std::min<uint64_t>(per, v->n_rows - r0);
-        c.rows = (const uint8_t *)v->rows + r0 * v->row_stride * v->char_width;
-        c.lengths = v->lengths ? v->lengths + r0 : nullptr;
-        rc = find_all_csr_host_one(p, &c, offsets + r0, start, end, capacity);
-        if (rc) return rc;
-    }
-    *total = offsets[v->n_rows];
-    return NEEDLE_OK;
+    rc = for_host_chunks(v, 16, [&](const needle_batch_view &c, uint64_t r0) { return find_all_csr_host_one(p, &c, offsets + r0, start, end, capacity); });
+    if (rc == NEEDLE_OK) *total = offsets[v->n_rows];
+    return rc;
 }
 static int find_all_host(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts, int32_t *start,
                          int32_t *end, int *more, uint32_t *start_end16) {
@@ -2770,20 +2608,12 @@ static int find_all_host(const needle_pattern *p, const needle_batch_view *v, ui
     if (more) *more = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!counts || (slots && !start_end16 && (!start || !end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
-    const uint64_t row_bytes = std::max<uint64_t>(16, (v->row_stride * v->char_width + 15) & ~(uint64_t)15) + 8 + 8ull * slots;
-    const uint64_t per = std::max<uint64_t>(64, (kHostChunkBytes / row_bytes) & ~(uint64_t)63);
     // (rows of at most 65 534 chars: an empty match at index 65 535 would read as an unfiled slot; NEEDLE_FIND_ALL_ROUNDS: the tests'
     // cross-check of the round-per-match form goes through needle_find_all_dev)
-    static const bool rounds_forced = getenv("NEEDLE_FIND_ALL_ROUNDS") && atoi(getenv("NEEDLE_FIND_ALL_ROUNDS")) != 0;
-    const bool packed_inside = !rounds_forced && (v->lengths ? v->row_stride : v->row_len) <= 65534u; // (lengths[r] <= row_stride: checked above)
+    const bool packed_inside = !find_all_rounds_forced() && (v->lengths ? v->row_stride : v->row_len) <= 65534u; // (lengths[r] <= row_stride: checked above)
     std::vector<uint32_t> stage;
-    for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
-        needle_batch_view c = *v;
-        c.n_rows = std::min<uint64_t>(per, v->n_rows - r0);
-        c.rows = (const uint8_t *)v->rows + r0 * v->row_stride * v->char_width;
-        c.lengths = v->lengths ? v->lengths + r0 : nullptr;
-        int m = 0;
+    return for_host_chunks(v, 8 + 8ull * slots, [&](const needle_batch_view &c, uint64_t r0) {
+        int m = 0, rc = NEEDLE_OK;
         if (!start_end16 && slots && packed_inside) {
             // int32 results wanted, rows of at most 65 535 chars: the one-dword form on the device and over PCIe (half the result
             // bytes both ways), opened into the caller's two arrays here on the host
@@ -2803,8 +2633,8 @@ static int find_all_host(const needle_pattern *p, const needle_batch_view *v, ui
             if (rc) return rc;
         }
         if (m && more) *more = 1;
-    }
-    return NEEDLE_OK;
+        return (int)NEEDLE_OK;
+    });
 }
 int needle_find_all_host(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts, int32_t *start,
                          int32_t *end, int *more) {

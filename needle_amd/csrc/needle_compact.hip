@@ -18,6 +18,7 @@
 #include <string>
 
 #include "../../include/needle_hip.h"
+#include "needle_launch.h"
 
 namespace needle {
 int set_error(int code, const std::string &msg);

@@ -14,6 +14,7 @@
 // indexBackwards is found afterwards, one lane per matched row (backward_row_kernel, needle_stripe.hip).  Everything else
 // takes the ordinary tiled kernel (needle_scan.h).
 #include "needle_walk.h"
+#include "needle_launch.h"
 
 namespace needle {
 

@@ -32,6 +32,7 @@
 // re-reads of ends and text all miss the L2.)
 #include "needle_walk.h"
 #include "needle_find_all.h"
+#include "needle_launch.h"
 
 namespace needle {
 

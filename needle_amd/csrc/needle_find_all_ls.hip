@@ -18,6 +18,7 @@
 // dword per match), compact filing at caller-computed offsets, or counting only.
 #include "needle_walk.h"
 #include "needle_find_all.h"
+#include "needle_launch.h"
 
 namespace needle {
 

@@ -3,6 +3,7 @@
 // (needle_scan_matches.hip / _contained.hip / _find1.hip / _find2.hip: the kernel template's instantiations compile
 // in parallel there).
 #include "needle_walk.h"
+#include "needle_launch.h"
 
 namespace needle {
 

@@ -1,0 +1,59 @@
+// Host-side launchers and shape / LDS-footprint queries of the kernels, as needle_api.cpp calls them.  Every file that defines one of them
+// includes this header, so a signature or a default argument that drifts apart fails to compile.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <functional>
+#include "needle_device.h"
+#include "needle_find_all.h"
+#include "needle_ngram.h"
+
+namespace needle {
+
+// needle_kernels.hip: the scan kernels of fixed-stride rows
+hipError_t launch_scan(int op, int char_width, const ScanArgs &a, int n_cus, hipStream_t stream);
+bool shape_for_program(const ProgHeader &h, int char_width, int *waves, int *chb, int *tiles_in_f_rows);
+// needle_packed_find2.hip, needle_packed_find_all2.hip: packed rows scanned where they lie
+hipError_t launch_packed(int op, int char_width, const PackedArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_packed_find_all(int char_width, const PackedFindAllArgs &a, int n_cus, hipStream_t stream);
+bool packed_find_all_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
+// needle_compact.hip
+int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
+                      const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill);
+// needle_find_all.hip, needle_find_all_ls.hip: every match of every row in one pass
+hipError_t launch_find_all(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream);
+hipError_t launch_find_all_lockstep(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream);
+bool find_all_lockstep_shape_ok(const FindAllArgs &fa);
+// needle_stripe.hip: few long rows (stripes, speculative stripes), the round-per-match find-all's collect pass, packed -> fixed stride
+hipError_t launch_find_all_collect(uint64_t n_rows, uint32_t slots, uint32_t k, const int32_t *s, const int32_t *e, int32_t *cursor,
+                                   uint32_t *counts, int32_t *starts, int32_t *ends, int32_t *any_hit, int n_cus, hipStream_t stream);
+hipError_t launch_long_rows(int char_width, const StripeArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_spec_len(const SpecArgs &a, hipStream_t stream);
+hipError_t launch_spec_init(const SpecArgs &a, hipStream_t stream);
+hipError_t launch_spec_fix(const SpecArgs &a, hipStream_t stream);
+hipError_t launch_spec_reduce(const SpecArgs &a, hipStream_t stream);
+hipError_t launch_backward_rows(int char_width, const StripeArgs &a, hipStream_t stream);
+hipError_t launch_unpack(const void *data, const uint64_t *offsets, uint64_t n_rows, uint32_t cw, void *out,
+                         uint64_t stride_bytes, uint32_t *lengths, int32_t *overflow, int n_cus, hipStream_t stream);
+#ifdef NEEDLE_TUNING // needle_dict.hip (two row sets per wave; measured, no faster -- DESIGN.md s4) is part of measurement builds only
+bool dict_kernel_applies(int char_width, const ScanArgs &a);
+hipError_t launch_dict(int op, const ScanArgs &a, int n_cus, hipStream_t stream);
+#endif
+// needle_ngram.hip: containedIn / find behind the n-gram candidate filter
+bool ngram_shape_ok(const ScanArgs &a);
+size_t ngram_lds_bytes(const ProgHeader &h, const NgramParams &ng);
+hipError_t launch_ngram(int op, const ScanArgs &a, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats, int n_cus, hipStream_t stream,
+                        int char_width = 1, int page = 0, int sub = 0xFF);
+size_t ngram_find_all_lds_bytes(const ProgHeader &h, const NgramParams &ng);
+hipError_t launch_ngram_find_all(const ScanArgs &a, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats, uint32_t slots, uint32_t *counts,
+                                 int32_t *starts, int32_t *ends, uint32_t *packed, int32_t *more, const uint64_t *offsets, bool count_only, int n_cus,
+                                 hipStream_t stream, int char_width, int page, int sub, uint32_t kshift);
+// needle_ngram_packed_find2.hip: the same filter in front of packed rows (needle_ngram_packed.h)
+size_t ngram_packed_lds_bytes(const ProgHeader &h, const NgramParams &ng);
+hipError_t launch_ngram_packed(int op, const ScanArgs &a, const uint64_t *offsets, int32_t *overflow, const NgramParams &ng, const uint32_t *d_bitmap,
+                               uint32_t *d_stats, int n_cus, hipStream_t stream, int char_width, int page, int sub);
+// needle_lower.cpp (NEEDLE_PREFILTER)
+int ngram_level();
+
+} // namespace needle

@@ -10,6 +10,7 @@
 //   * ragged rows              -> a PAD column (identity for matches/containedIn, sink for the index walks)
 //   * wasAccepted<X>(state)    -> states renumbered so that accepted(s) == (s >= A0)
 #include "needle_lower.h"
+#include "needle_launch.h"
 #include "needle_ngram_host.h"
 #include <algorithm>
 #include <array>

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <vector>
 #include "needle_ngram_kernel.h"
+#include "needle_launch.h"
 
 namespace needle {
 

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "needle_ngram_packed.h"
+#include "needle_launch.h"
 namespace needle {
 hipError_t launch_ngram_packed_contained1(const NgramArgs &A, int n_cus, size_t lds, hipStream_t s);
 hipError_t launch_ngram_packed_contained2(const NgramArgs &A, int n_cus, size_t lds, hipStream_t s);

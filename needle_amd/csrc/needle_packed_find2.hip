@@ -1,8 +1,8 @@
 // Instantiations of the packed-rows scan kernel for find() on UTF-16 rows; the launcher of the packed-rows scan (shape: the
 // tiled scan's, from the automaton's LDS footprint -- a wave's window is the tile of that shape).
 #include "needle_packed.h"
+#include "needle_launch.h"
 namespace needle {
-bool shape_for_program(const ProgHeader &h, int char_width, int *waves, int *chb, int *tiles_in_f_rows); // needle_kernels.hip
 hipError_t launch_packed_matches(const PackedArgs &a, int cw, PackedShape sh, hipStream_t s);
 hipError_t launch_packed_contained_in(const PackedArgs &a, int cw, PackedShape sh, hipStream_t s);
 hipError_t launch_packed_find1(const PackedArgs &a, PackedShape sh, hipStream_t s);

@@ -1,6 +1,7 @@
 // Instantiations of the packed-rows find-all kernel for UTF-16 rows; its shape and launcher (one persistent workgroup per CU, the
 // shape from the transducer's LDS footprint as launch_find_all_lockstep chooses it).
 #include "needle_packed_find_all.h"
+#include "needle_launch.h"
 namespace needle {
 hipError_t launch_packed_find_all1(const PackedFindAllArgs &a, int chb, int grid, int waves, size_t lds, hipStream_t s);
 

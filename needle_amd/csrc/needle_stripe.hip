@@ -5,6 +5,7 @@
 //                                      (intra-row parallelism for packed-mode automata)
 //   short_kernel                       rows of at most 64 bytes: register-resident, no LDS transposition
 #include "needle_walk.h"
+#include "needle_launch.h"
 
 namespace needle {
 

@@ -80,7 +80,7 @@ def _acc(d):
 
 
 def from_pattern(p, op):
-    """The automaton run_dev puts behind the filter: containedIn's, the lengths automaton, or (one-length patterns) indexForwards'."""
+    """The automaton choose_route (needle_api.cpp) puts behind the filter: containedIn's, the lengths automaton, or (one-length patterns) indexForwards'."""
     t = p.tables()
     cm = t["class_map"]
     if op == "contained_in":

@@ -1,5 +1,5 @@
 """containedIn() / find() of PACKED device batches behind the n-gram candidate filter (needle_amd/csrc/needle_ngram_packed.h; routing:
-run_packed_dev in needle_api.cpp).  Every case is checked against the CPU oracle on every row (DFAClassBuilder.java:335-471, 625-659,
+choose_route / run_packed_dev in needle_api.cpp).  Every case is checked against the CPU oracle on every row (DFAClassBuilder.java:335-471, 625-659,
 1004-1022 restated by oracle/) and, bit for bit, against the same call with the filter pinned OFF (the plain packed kernel of
 needle_packed.h).  `filter_launches` of needle_pattern_prefilter_state says which kernel ran: it rises by one per packed call behind the
 filter and does not move under OFF or with NEEDLE_PREFILTER_PACKED=0.
@@ -289,7 +289,7 @@ def test_mixed_scripts_wide_filter():
 
 @pytest.mark.gpu
 def test_pattern_with_char_ff_and_union_without_filter():
-    """`abcdefÿgh|bcdefgh` takes whatever route run_dev gives it (a filter at NEEDLE_PREFILTER=2 only); the six-name union has no filter:
+    """`abcdefÿgh|bcdefgh` takes whatever route choose_route gives it (a filter at NEEDLE_PREFILTER=2 only); the six-name union has no filter:
     the route declines and filter_launches stays put."""
     rng = np.random.default_rng(4)
     p, o = compiled("abcdefÿgh|bcdefgh")
