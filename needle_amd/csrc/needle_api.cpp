@@ -1036,6 +1036,79 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
     return NEEDLE_OK;
 }
 
+// The program the PER-LANE find-all kernels walk for this pattern on rows of cw -- find_all_kernel (fixed-stride rows, needle_find_all.hip)
+// and packed_find_all_lane_kernel (packed rows, needle_packed_find_all_lane.h) -- and how its matches find their starts: one choice for
+// both layouts.  Asked through `get`, which answers with a variant's program header (nullptr: the pattern has none): get_program on a
+// device, a host-side lowering for needle_pattern_find_all_packed_route.
+struct LaneChoice {
+    Variant variant = V_FA_PLAIN; // the forward program
+    const ProgHeader *hdr = nullptr;
+    bool lmode = false;         // the "lengths" automaton: start = end - pend[end state]
+    bool need_backward = false; // starts by indexBackwards on the backward program
+    uint32_t defer = 0;         // FindAllArgs::defer
+};
+static int find_all_lengths_level() {
+    static const int v = getenv("NEEDLE_FIND_ALL_LENGTHS") ? atoi(getenv("NEEDLE_FIND_ALL_LENGTHS")) : 1;
+    return v;
+}
+template <class Get>
+static int find_all_lane_choice(const needle_pattern *p, bool count_only, Get &&get, LaneChoice *c) {
+    *c = LaneChoice();
+    c->need_backward = p->t.fixed_len < 0;
+    int rc = NEEDLE_OK;
+    // start = end - (the match length the automaton's end state remembers): no backward walks at all, when the pattern
+    // allows it (needle_lower.h: keyword unions and the like).  NEEDLE_FIND_ALL_LENGTHS=0: off (A/B, tests).
+    const int lengths_level = find_all_lengths_level();
+    if (c->need_backward && lengths_level != 0 && !count_only) {
+        if ((rc = get(V_FA_LENGTHS, &c->hdr))) return rc;
+        c->lmode = c->hdr != nullptr;
+        c->variant = V_FA_LENGTHS;
+        if (!c->lmode && lengths_level > 1 && find_lengths_for(MODE_SPARSE)) {
+            // no plain LDS table holds the lengths automaton (a big dictionary): the scan kernels' compressed form of it, if there is
+            // one.  Opt-in (NEEDLE_FIND_ALL_LENGTHS=2): measured on C3-sparse (profiles/r04_find_all.md) it is no faster than hot rows +
+            // backward walks, 2.05 against 1.98 ms -- the per-lane piece walk is what costs there, not the 0.25 starts per row
+            const ProgHeader *sp = nullptr;
+            if ((rc = get(V_LENGTHS, &sp))) return rc;
+            if (sp && sp->mode == MODE_SPARSE) c->hdr = sp, c->lmode = true, c->variant = V_LENGTHS;
+        }
+        if (c->lmode) c->need_backward = false;
+    }
+    if (!c->lmode) {
+        c->variant = c->need_backward ? V_FA_BACKMAPS : V_FA_PLAIN;
+        if ((rc = get(c->variant, &c->hdr))) return rc;
+        if (!c->hdr) return fail(NEEDLE_ERR_UNSUPPORTED, "find_all: the pattern has no program");
+    }
+    static const bool no_defer = (getenv("NEEDLE_FIND_ALL_DEFER") ? atoi(getenv("NEEDLE_FIND_ALL_DEFER")) : 1) == 0; // A/B, tests
+    c->defer = (p->t.fixed_len < 0 && !c->hdr->root_accepting && !no_defer && !c->lmode) ? 1u : 0u;
+#ifdef NEEDLE_TUNING // measurement builds only: start = the search cursor (wrong answers; never in the shipping library)
+    if (c->defer && debug_no_backward()) c->defer = 2;
+#endif
+    return NEEDLE_OK;
+}
+// The choice on the current device: the programs themselves.
+struct LaneProgram {
+    const DevProgram *fp = nullptr, *bp = nullptr;
+    bool lmode = false;
+    uint32_t defer = 0;
+    int n_cus = 0;
+};
+static int find_all_lane_program(needle_pattern *p, int cw, bool count_only, LaneProgram *lp) {
+    *lp = LaneProgram();
+    LaneChoice c;
+    int rc = find_all_lane_choice(p, count_only, [&](Variant v, const ProgHeader **h) {
+        const DevProgram *dp = nullptr;
+        const int r = get_program(p, W_FORWARDS, cw, v, &dp, &lp->n_cus);
+        *h = (r == NEEDLE_OK && dp) ? &dp->prog.hdr : nullptr;
+        return r;
+    }, &c);
+    if (rc) return rc;
+    if ((rc = get_program(p, W_FORWARDS, cw, c.variant, &lp->fp, &lp->n_cus))) return rc; // (resident by now)
+    lp->lmode = c.lmode;
+    lp->defer = c.defer;
+    if (c.need_backward && (rc = backward_program(p, cw, &lp->bp))) return rc;
+    return NEEDLE_OK;
+}
+
 // The "more" flag of a one-pass find-all launch: a zeroed scratch word the kernel sets when some row has a match beyond its last slot.
 // launch(d_more) enqueues the kernel (and what belongs behind it); the flag is read back -- the call's only synchronisation -- only when the
 // caller asked whether its slots sufficed (more != nullptr).
@@ -1551,6 +1624,44 @@ static int packed_find_all_launch(const needle_packed_view *v, const DevProgram 
     return NEEDLE_OK;
 }
 
+// The one answer to "does this per-lane find-all program take the packed per-lane kernel on rows of char_width"
+// (needle_packed_find_all_lane.h): a packed-function or LDS-table program whose image and the windows of at least the smallest shape
+// fit the LDS.  Hot-rows, HBM-table and compressed programs go by conversion.  NEEDLE_PACKED_FIND_ALL_LANE=0: off (A/B, tests: the
+// conversion route).  The routing below and needle_pattern_find_all_packed_route both ask it.
+static bool packed_find_all_lane_takes(const ProgHeader &h, int char_width) {
+    static const bool lane_on = (getenv("NEEDLE_PACKED_FIND_ALL_LANE") ? atoi(getenv("NEEDLE_PACKED_FIND_ALL_LANE")) : 1) != 0;
+    int waves = 0, chb = 0;
+    return lane_on && packed_find_all_lane_mode(h.mode) && packed_find_all_lane_shape(h.lds_bytes, char_width, &waves, &chb);
+}
+
+// Patterns without a transducer whose per-lane program the packed per-lane kernel takes: one stream-ordered launch on the packed text,
+// no offsets read-back, no chunks.  *taken = false: the pattern goes by conversion.
+static int packed_find_all_lane(needle_pattern *p, const needle_packed_view *v, uint32_t *d_counts, const uint64_t *d_offsets, int32_t *d_start,
+                                int32_t *d_end, bool count_only, int *more, hipStream_t stream, bool *taken) {
+    *taken = false;
+    const int cw = (int)v->char_width;
+    LaneProgram lp;
+    int rc = find_all_lane_program(p, cw, count_only, &lp);
+    if (rc) return rc;
+    if (!packed_find_all_lane_takes(lp.fp->prog.hdr, cw)) return NEEDLE_OK;
+    *taken = true;
+    PackedFindAllArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f.s = scan_args(v, lp.fp, lp.bp, p->t.fixed_len, ScanOut());
+    a.f.counts = d_counts;
+    a.f.offsets = d_offsets;
+    a.f.starts = d_start;
+    a.f.ends = d_end;
+    a.f.count_only = count_only ? 1u : 0u;
+    a.f.lmode = lp.lmode ? 1u : 0u;
+    a.f.defer = lp.defer;
+    a.row_offsets = v->offsets;
+    return with_more_flag(stream, more, "find_all (packed per-lane kernel)", [&](int32_t *d_more) {
+        a.f.more = d_more;
+        return launch_packed_find_all_lane(cw, a, lp.n_cus, stream);
+    });
+}
+
 // Patterns without a packed find-all program: the offsets are read back ONCE (a synchronisation of the stream), consecutive rows are
 // converted chunk by chunk -- each chunk at its own stride, its padded bytes within 4x its text + 64 KiB -- by needle_rows_from_packed_dev
 // and run through the fixed-stride entry.  Per-row counts and absolute CSR offsets need no merge step.
@@ -1624,6 +1735,9 @@ int needle_count_matches_packed_dev(const needle_pattern *cp, const needle_packe
     rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
     if (rc) return rc;
     if (tp) return packed_find_all_launch(v, tp, n_cus, d_counts, nullptr, nullptr, nullptr, 0, nullptr, true, nullptr, nullptr, (hipStream_t)stream_);
+    bool taken = false;
+    rc = packed_find_all_lane(p, v, d_counts, nullptr, nullptr, nullptr, true, nullptr, (hipStream_t)stream_, &taken);
+    if (rc || taken) return rc;
     return packed_find_all_by_conversion(p, v, d_counts, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
 }
 
@@ -1640,6 +1754,9 @@ int needle_find_all_csr_packed_dev(const needle_pattern *cp, const needle_packed
     rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
     if (rc) return rc;
     if (tp) return packed_find_all_launch(v, tp, n_cus, nullptr, d_offsets, d_start, d_end, 0, nullptr, false, more, nullptr, (hipStream_t)stream_);
+    bool taken = false;
+    rc = packed_find_all_lane(p, v, nullptr, d_offsets, d_start, d_end, false, more, (hipStream_t)stream_, &taken);
+    if (rc || taken) return rc;
     return packed_find_all_by_conversion(p, v, nullptr, d_offsets, d_start, d_end, more, (hipStream_t)stream_);
 }
 
@@ -2181,6 +2298,39 @@ int needle_pattern_find_all_transducer(const needle_pattern *cp, int char_width,
     return NEEDLE_OK;
 }
 
+// Which route needle_count_matches_packed_dev (count_only) / needle_find_all_csr_packed_dev take for this pattern on rows of char_width:
+// 0 conversion, 1 the transducer kernel, 2 the per-lane kernel.  Answers without a device: the programs are lowered on the host, the
+// questions are the entries' own (packed_find_all_takes by way of needle_pattern_find_all_transducer, find_all_lane_choice,
+// packed_find_all_lane_takes).
+int needle_pattern_find_all_packed_route(const needle_pattern *cp, int char_width, int count_only, int32_t *route) {
+    if (!cp || !route || (char_width != 1 && char_width != 2) || (count_only != 0 && count_only != 1)) return fail(NEEDLE_ERR_INVALID, "bad argument");
+    *route = 0;
+    int32_t transducer = 0;
+    int rc = needle_pattern_find_all_transducer(cp, char_width, &transducer, nullptr, nullptr, 0, nullptr);
+    if (rc) return rc;
+    if (transducer) {
+        *route = 1;
+        return NEEDLE_OK;
+    }
+    Program pr; // the one program the choice settles on (asked for last)
+    LaneChoice c;
+    rc = find_all_lane_choice(cp, count_only != 0, [&](Variant v, const ProgHeader **h) {
+        *h = nullptr;
+        if (v == V_FA_LENGTHS || v == V_LENGTHS) { // (as get_program lowers them)
+            const MatchLengths *ml = pattern_ml(cp);
+            if (!ml) return (int)NEEDLE_OK;
+            pr = lower_match_lengths(cp->t, *ml, char_width, max_prog_lds(), v == V_FA_LENGTHS);
+        } else {
+            pr = lower(cp->t, W_FORWARDS, char_width, max_prog_lds(), false, v == V_FA_BACKMAPS, true);
+        }
+        if (!pr.blob.empty()) *h = &pr.hdr;
+        return (int)NEEDLE_OK;
+    }, &c);
+    if (rc) return rc;
+    if (packed_find_all_lane_takes(*c.hdr, char_width)) *route = 2;
+    return NEEDLE_OK;
+}
+
 int needle_pattern_get_class_map(const needle_pattern *p, uint8_t *cm) {
     if (!p || !cm) return fail(NEEDLE_ERR_INVALID, "NULL argument");
     memcpy(cm, p->t.class_map.data(), 65536);
@@ -2351,30 +2501,8 @@ static int find_all_one_pass(needle_pattern *p, const needle_batch_view *v, uint
     const int cw = (int)v->char_width;
     const uint64_t stride_bytes = v->row_stride * v->char_width;
     if (stride_bytes >= (1ull << 26)) return fail(NEEDLE_ERR_UNSUPPORTED, "rows of 64 MiB or more: only needle_find_all_dev (round per match) takes them");
-    const DevProgram *fp = nullptr, *bp = nullptr;
-    int n_cus = 0;
-    bool need_backward = p->t.fixed_len < 0;
     int rc = NEEDLE_OK;
-    // start = end - (the match length the automaton's end state remembers): no backward walks at all, when the pattern
-    // allows it (needle_lower.h: keyword unions and the like).  NEEDLE_FIND_ALL_LENGTHS=0: off (A/B, tests).
-    static const int lengths_level = getenv("NEEDLE_FIND_ALL_LENGTHS") ? atoi(getenv("NEEDLE_FIND_ALL_LENGTHS")) : 1;
-    const bool lengths_on = lengths_level != 0;
-    bool lmode = false;
-    if (need_backward && lengths_on && !count_only) {
-        rc = get_program(p, W_FORWARDS, cw, V_FA_LENGTHS, &fp, &n_cus);
-        if (rc) return rc;
-        lmode = fp != nullptr;
-        if (!lmode && lengths_level > 1 && find_lengths_for(MODE_SPARSE)) {
-            // no plain LDS table holds the lengths automaton (a big dictionary): the scan kernels' compressed form of it, if there is
-            // one.  Opt-in (NEEDLE_FIND_ALL_LENGTHS=2): measured on C3-sparse (profiles/r04_find_all.md) it is no faster than hot rows +
-            // backward walks, 2.05 against 1.98 ms -- the per-lane piece walk is what costs there, not the 0.25 starts per row
-            const DevProgram *sp = nullptr;
-            rc = get_program(p, W_FORWARDS, cw, V_LENGTHS, &sp, &n_cus);
-            if (rc) return rc;
-            if (sp && sp->prog.hdr.mode == MODE_SPARSE) fp = sp, lmode = true;
-        }
-        if (lmode) need_backward = false;
-    }
+    static const bool lengths_on = find_all_lengths_level() != 0;
     // the find-all outputs, common to the three kernels below (s: the rows and the program, filled by each)
     FindAllArgs fa;
     memset(&fa, 0, sizeof(fa));
@@ -2450,16 +2578,12 @@ static int find_all_one_pass(needle_pattern *p, const needle_batch_view *v, uint
             });
         }
     }
-    if (!lmode) rc = get_program(p, W_FORWARDS, cw, need_backward ? V_FA_BACKMAPS : V_FA_PLAIN, &fp, &n_cus);
-    if (rc) return rc;
-    if (need_backward && (rc = backward_program(p, cw, &bp))) return rc;
-    fa.s = scan_args(v, stride_bytes, fp, bp, p->t.fixed_len, ScanOut());
-    fa.lmode = lmode ? 1u : 0u;
-    static const bool no_defer = (getenv("NEEDLE_FIND_ALL_DEFER") ? atoi(getenv("NEEDLE_FIND_ALL_DEFER")) : 1) == 0; // A/B, tests
-    fa.defer = (fa.s.fixed_len < 0 && !fa.s.hdr.root_accepting && !no_defer && !lmode) ? 1u : 0u;
-#ifdef NEEDLE_TUNING // measurement builds only: start = the search cursor (wrong answers; never in the shipping library)
-    if (fa.defer && debug_no_backward()) fa.defer = 2;
-#endif
+    LaneProgram lp;
+    if ((rc = find_all_lane_program(p, cw, count_only, &lp))) return rc;
+    fa.s = scan_args(v, stride_bytes, lp.fp, lp.bp, p->t.fixed_len, ScanOut());
+    fa.lmode = lp.lmode ? 1u : 0u;
+    fa.defer = lp.defer;
+    const int n_cus = lp.n_cus;
     return with_more_flag(stream, more, "find_all", [&](int32_t *d_more) {
         fa.more = d_more;
         return launch_find_all(cw, fa, n_cus, stream);

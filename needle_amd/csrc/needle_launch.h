@@ -18,6 +18,10 @@ bool shape_for_program(const ProgHeader &h, int char_width, int *waves, int *chb
 hipError_t launch_packed(int op, int char_width, const PackedArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_packed_find_all(int char_width, const PackedFindAllArgs &a, int n_cus, hipStream_t stream);
 bool packed_find_all_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
+// needle_packed_find_all_lane2.hip: every match of every packed row for patterns without a transducer (per-lane restarts)
+hipError_t launch_packed_find_all_lane(int char_width, const PackedFindAllArgs &a, int n_cus, hipStream_t stream);
+bool packed_find_all_lane_mode(uint32_t mode);
+bool packed_find_all_lane_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
 // needle_compact.hip
 int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
                       const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill);

@@ -264,6 +264,14 @@ class Pattern:
         out["blob"] = blob
         return out
 
+    def find_all_packed_route(self, char_width=1, count_only=False):
+        """The route count_matches_packed (count_only) / find_all_packed take for this pattern on packed device rows of char_width
+        (needle_pattern_find_all_packed_route; no device needed): "conversion" (to fixed-stride rows, offsets read back), "transducer"
+        (the lock-step transducer kernel) or "lane" (the per-lane restart kernel)."""
+        route = ctypes.c_int32(0)
+        _check(_lib.lib().needle_pattern_find_all_packed_route(self._h, int(char_width), 1 if count_only else 0, ctypes.byref(route)))
+        return ("conversion", "transducer", "lane")[route.value]
+
     def tables(self):
         """The pattern's tables in the reference layout (class map, stride, 4 x (table, accepting, max_char))."""
         inf = self.info()

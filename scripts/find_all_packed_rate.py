@@ -12,7 +12,14 @@ Per route: matches, a start / end checksum (all must agree), the median ms per s
 bytes (compact16: offsets + 4 B per match; CSR: 4 B count per row + offsets + 8 B per match) -- and that rate's share of 8 TB/s.
 The compact16 routes' scratch (n_rows / 64 x max_per_row x 256 B: 5 GB here) is above the library's default scratch keep (512 MB): this
 script raises NEEDLE_SCRATCH_KEEP_MB (unless set) so that no timed step pays a fresh driver allocation.
-python scripts/find_all_packed_rate.py [--rows N] [--steps K] [--warmup W] [--only c2p,c3p] [--max-per-row M]"""
+Patterns WITHOUT a transducer (--only c3np,c2n): count + CSR fill through the packed entries on (a) the per-lane kernel
+(needle_packed_find_all_lane.h) and (b) the conversion route (NEEDLE_PACKED_FIND_ALL_LANE=0).  The switch is read once per process, so
+every route runs in a child of its own, alternating (a, b, a, b), one GPU process at a time, each under its own time limit; totals
+and start / end checksums must agree.
+  c3np  c3p's text, the dictionary extended by w[:3] and w[3:-1] of the first 100 keywords of at least --nested-min-len chars, longest
+        first (a nested dictionary: no transducer -- asserted)
+  c2n   c2p's text, the nullable `[0-9]*`
+python scripts/find_all_packed_rate.py [--rows N] [--steps K] [--warmup W] [--only c2p,c3p,c3np,c2n] [--max-per-row M]"""
 import argparse
 import ctypes
 import json
@@ -26,14 +33,129 @@ HBM_PEAK_GBS = 8000.0
 os.environ.setdefault("NEEDLE_SCRATCH_KEEP_MB", "16384")
 
 
+LANE_WORKLOADS = ("c3np", "c2n")
+
+
+def lane_pattern(wl, nested_min_len):
+    """(pattern, label, the base workload whose rows it scans, its planted words)"""
+    import bench
+    from needle_amd.pattern import DFACompiler
+    if wl == "c2n":
+        _, _, words = bench.make_pattern("c2")
+        return DFACompiler.compile("[0-9]*", "DigitStar"), "'[0-9]*' (nullable) over c2p's text", "c2", words
+    _, _, words = bench.make_pattern("c3")
+    long = [w for w in words if len(w) >= nested_min_len][:100]
+    ext = sorted(set(words) | {w[:3] for w in long} | {w[3:-1] for w in long if w[3:-1]}, key=lambda w: (-len(w), w))
+    return (DFACompiler.compile("|".join(ext), "Keywords1kNested"),
+            "union-of-1k-keywords + %d prefixes / middles of %d keywords of >= %d chars (nested) over c3p's text" % (len(ext) - len(set(words)), len(long), nested_min_len),
+            "c3", words)
+
+
+def lane_child(args, wl):
+    """One workload on the route this process's environment selects: count + cumsum + CSR fill, timed by events."""
+    import torch
+    import bench
+    from needle_amd import _lib
+    L = _lib.lib()
+    dev = torch.device("cuda", 0)
+    n = args.rows
+    pattern, what, base, words = lane_pattern(wl, args.nested_min_len)
+    assert pattern.find_all_transducer(1) is None, "%s: the pattern has a transducer" % wl
+    route = pattern.find_all_packed_route(1, False)
+    assert route == pattern.find_all_packed_route(1, True)
+    lens = (torch.arange(n, device=dev, dtype=torch.int64) * 2654435761 % 256 + 1)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(lens, 0)
+    col = torch.arange(256, device=dev)[None, :]
+    chars = int(offsets[-1].item())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = bench.make_rows(base, words, 0, n, dev)
+    data = torch.empty(chars, dtype=torch.uint8, device=dev)
+    for s in range(0, n, 1 << 20):
+        k = min(1 << 20, n - s)
+        data[int(offsets[s].item()):int(offsets[s + k].item())] = rows[s:s + k][col < lens[s:s + k, None]]
+    del rows
+    pv = _lib.PackedView()
+    pv.data, pv.char_width, pv.n_rows, pv.offsets = data.data_ptr(), 1, n, offsets.data_ptr()
+    h = pattern._h
+
+    def check(rc):
+        assert rc == 0, L.needle_last_error()
+
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    check(L.needle_count_matches_packed_dev(h, ctypes.byref(pv), counts.data_ptr(), stream))
+    m = int(counts.to(torch.int64).sum().item())
+    csr_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    st = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
+    en = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
+
+    def step():
+        check(L.needle_count_matches_packed_dev(h, ctypes.byref(pv), counts.data_ptr(), stream))
+        torch.cumsum(counts, 0, out=csr_off[1:])
+        check(L.needle_find_all_csr_packed_dev(h, ctypes.byref(pv), csr_off.data_ptr(), st.data_ptr(), en.data_ptr(), None, stream))
+
+    step()
+    torch.cuda.synchronize()
+    assert int(csr_off[-1].item()) == m
+    sums = (m, int(st.to(torch.int64).sum().item()), int(en.to(torch.int64).sum().item()))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for r in range(args.warmup + args.steps):
+        e0.record()
+        step()
+        e1.record()
+        e1.synchronize()
+        if r >= args.warmup:
+            ms.append(e0.elapsed_time(e1))
+    actual = chars + n * 8 + (n * 8 + 8) + n * 4 + m * 8
+    med = sorted(ms)[len(ms) // 2]
+    print(json.dumps({"workload": wl, "what": what, "route": route, "rows": n, "chars": chars, "matches": sums[0], "checksum_start": sums[1],
+                      "checksum_end": sums[2], "ms": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                      "GB/s": round(actual / med / 1e6, 1), "actual_bytes": actual}), flush=True)
+
+
+def lane_parent(args, wl):
+    """(a) lane, (b) conversion, (a), (b): one child at a time.  This process never opens the GPU."""
+    import subprocess
+    runs = []
+    for tag, env_val in (("a", "1"), ("b", "0"), ("a", "1"), ("b", "0")):
+        env = dict(os.environ, NEEDLE_PACKED_FIND_ALL_LANE=env_val)
+        cmd = [sys.executable, os.path.abspath(__file__), "--lane-child", wl, "--rows", str(args.rows), "--steps", str(args.steps),
+               "--warmup", str(args.warmup), "--nested-min-len", str(args.nested_min_len)]
+        r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, timeout=args.child_timeout, check=True)
+        out = json.loads(r.stdout.decode().strip().split("\n")[-1])
+        assert out["route"] == ("lane" if tag == "a" else "conversion"), out
+        out["tag"] = tag
+        runs.append(out)
+        print(json.dumps(out), flush=True)
+    same = {(r["matches"], r["checksum_start"], r["checksum_end"]) for r in runs}
+    assert len(same) == 1, same  # every route and run: the same matches
+    a = [r["ms"] for r in runs if r["tag"] == "a"]
+    b = [r["ms"] for r in runs if r["tag"] == "b"]
+    print(json.dumps({"workload": wl, "summary": True, "matches": runs[0]["matches"], "lane_ms": a, "conversion_ms": b,
+                      "lane_over_conversion": round((sum(a) / len(a)) / (sum(b) / len(b)), 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lane-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--nested-min-len", type=int, default=5)  # (c3's keywords have 3..5 chars: its longest)
+    ap.add_argument("--child-timeout", type=int, default=420)
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default="c2p,c3p")
     ap.add_argument("--max-per-row", type=int, default=128)
     args = ap.parse_args()
+    if args.lane_child:
+        return lane_child(args, args.lane_child)
+    wanted = args.only.split(",")
+    for wl in wanted:
+        if wl in LANE_WORKLOADS:
+            lane_parent(args, wl)
+    args.only = ",".join(w for w in wanted if w not in LANE_WORKLOADS)
+    if not args.only:
+        return
     import torch
     import bench
     from needle_amd import _lib

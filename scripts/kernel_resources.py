@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""VGPRs / scratch of every instantiation of the tiled scan kernel, of the packed-rows scan kernel, of the packed-rows find-all kernel
+"""VGPRs / scratch of every instantiation of the tiled scan kernel, of the packed-rows scan kernel, of the packed-rows find-all kernels
+(transducer and per-lane)
 and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip)
 (cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
@@ -15,7 +16,7 @@ tmp = tempfile.mkdtemp()
 for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", "needle_scan_find2",
            "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2", "needle_packed_next1",
            "needle_packed_next2", "needle_packed_forms1", "needle_packed_forms2",
-           "needle_packed_find_all1", "needle_packed_find_all2",
+           "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
            "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
@@ -52,6 +53,11 @@ for k, sc, v in sorted(rows):
     m = re.search(r"packed_find_all_kernelILi(\d)ELi(\d+)ELb(\d)E", k)
     if m:
         print("%4d %4d  find-all    cw%s %-8s window %5d B" % (sc, v, m.group(1), "run" if m.group(3) == "1" else "lengths", 64 * int(m.group(2))))
+print("packed-rows per-lane find-all kernels (needle_packed_find_all_lane.h): scratch bytes / VGPRs / kernel / LDS window per wave")
+for k, sc, v in sorted(rows):
+    m = re.search(r"packed_find_all_lane_kernelILi(\d)ELi(\d)ELi(\d+)ELb(\d)E", k)
+    if m:
+        print("%4d %4d  find-all    cw%s %-8s %-11s window %5d B" % (sc, v, m.group(1), modes[m.group(2)], "skip-states" if m.group(4) == "1" else "", 64 * int(m.group(3))))
 # the n-gram filter kernels (needle_ngram_kernel.h): LDS = program + bitmaps + per wave the queues and slots (packed rows: + the row starts)
 names_ng = dict(names, **{"3": "find-all"})
 for title, rx in (("n-gram filter kernels, fixed-stride rows (needle_ngram.hip): scratch bytes / VGPRs / kernel", r"ngram_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d)ELb(\d)ELb(\d)E"),
