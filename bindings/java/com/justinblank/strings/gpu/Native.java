@@ -121,6 +121,12 @@ final class Native {
      */
     static native int prefilterState(long handle, int which, int[] state, float[] rate, long[] counts);
 
+    /**
+     * needle_pattern_find_all_packed_filter (charWidth 1 or 2, countOnly 0 or 1): out[0] = 1 when the packed find-all entries take the
+     * n-gram filter kernel for this pattern (neither the transducer nor the per-lane kernel takes it and a filter program exists).
+     */
+    static native int findAllPackedFilter(long handle, int charWidth, int countOnly, int[] out);
+
     /** needle_pattern_utf16_route: out[0] = the pattern's one page of the BMP (-1: it spans several), out[1] = the substitute byte. */
     static native int utf16Route(long handle, int[] out);
 

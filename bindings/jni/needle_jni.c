@@ -276,6 +276,18 @@ NATIVE(jint, prefilterState)(JNIEnv *env, jclass c, jlong h, jint which, jintArr
     return NEEDLE_OK;
 }
 
+/* needle_pattern_find_all_packed_filter: out[0] = 1 when the packed find-all entries take the filter kernel for this pattern */
+NATIVE(jint, findAllPackedFilter)(JNIEnv *env, jclass c, jlong h, jint charWidth, jint countOnly, jintArray out) {
+    int32_t available = 0;
+    const int rc = needle_pattern_find_all_packed_filter((const needle_pattern *)(intptr_t)h, charWidth, countOnly, &available);
+    if (rc != NEEDLE_OK) return rc;
+    if (int_room(env, out, 1)) {
+        const jint v[1] = {available};
+        (*env)->SetIntArrayRegion(env, out, 0, 1, v);
+    }
+    return NEEDLE_OK;
+}
+
 /* needle_pattern_utf16_route: out[0] = page (-1: none), out[1] = substitute byte */
 NATIVE(jint, utf16Route)(JNIEnv *env, jclass c, jlong h, jintArray out) {
     int32_t page = -1, sub = 0;

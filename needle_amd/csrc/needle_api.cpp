@@ -7,6 +7,7 @@
 #include <cstring>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -214,15 +215,15 @@ static const MatchLengths *pattern_ml(const needle_pattern *cp) {
     return p->ml_state > 0 ? &p->ml : nullptr;
 }
 
-static int get_program(needle_pattern *p, int which, int cw, Variant variant, const DevProgram **out, int *n_cus) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    // cw = 1 | page << 8: the BYTE program of the pattern rebased to one page of the BMP (UTF-16 rows narrowed on the fly: utf16_route)
-    const int page = cw >> 8, cw_key = cw;
-    cw &= 0xFF;
-    const bool wants_ml = variant == V_FA_LENGTHS || variant == V_LENGTHS || variant == V_FA_TRANSDUCER || ((variant == V_FILTER_HBM || variant == V_FILTER_WIDE) && which == W_FORWARDS && p->t.fixed_len < 0);
-    const MatchLengths *ml67 = wants_ml ? pattern_ml(p) : nullptr; // (before p->mu: see ml_mu)
-    std::lock_guard<std::mutex> lk(p->mu);
+// Whether lowering `variant` asks for the pattern's match-length analysis (pattern_ml: taken BEFORE p->mu, see ml_mu)
+static bool variant_wants_ml(const needle_pattern *p, int which, Variant variant) {
+    return variant == V_FA_LENGTHS || variant == V_LENGTHS || variant == V_FA_TRANSDUCER ||
+           ((variant == V_FILTER_HBM || variant == V_FILTER_WIDE) && which == W_FORWARDS && p->t.fixed_len < 0);
+}
+// The tables a program of char width cw | page << 8 is lowered from (under p->mu): the pattern's own, or -- page != 0 -- rebased to that
+// page of the BMP; *ml (when given) is moved along.
+static const RefTables *tables_for_page(needle_pattern *p, int page, const MatchLengths **ml) {
+    const MatchLengths *ml67 = *ml;
     const RefTables *tt = &p->t;
     if (page) { // chars page << 8 | b become bytes b: the class map's page in front, every automaton's maxChar moved along
         auto pit = p->page_tables.find(page);
@@ -243,6 +244,45 @@ static int get_program(needle_pattern *p, int which, int cw, Variant variant, co
         tt = &pit->second.t;
         if (ml67) ml67 = &pit->second.ml;
     }
+    *ml = ml67;
+    return tt;
+}
+// One variant's program, lowered on the host: what get_program makes resident, and what the host-side route queries look at.  false: the
+// pattern has no such program (no bounded match lengths, no filter, not a pattern of runs, no plain LDS table for the lengths form).
+static bool lower_variant(const RefTables &tt, int which, int cw, Variant variant, bool wants_ml, const MatchLengths *ml67, Program *out) {
+    if (variant == V_FILTER_HBM || variant == V_FILTER_WIDE || variant == V_FILTER_UNBOUNDED) {
+        if ((wants_ml && !ml67) || (variant == V_FILTER_WIDE && cw != 2) || (variant == V_FILTER_UNBOUNDED && (which != W_FORWARDS || cw != 1))) return false;
+        *out = variant == V_FILTER_WIDE ? lower_filter_wide(tt, (Which)which, ml67)
+                                        : lower_filter_hbm(tt, (Which)which, variant == V_FILTER_UNBOUNDED ? nullptr : ml67, variant == V_FILTER_UNBOUNDED);
+        return !out->blob.empty() && out->ng.p.on; // (no filter: the ordinary program is what runs)
+    }
+    if (variant == V_FA_RUNS) { // (absent when the pattern is not one of runs)
+        *out = lower_find_all_runs(tt, cw, max_prog_lds());
+        return !out->blob.empty();
+    }
+    if (variant == V_FA_LENGTHS || variant == V_LENGTHS || variant == V_FA_TRANSDUCER) {
+        // "lengths" form: the refined forward automaton + pend[] (needle_lower.h); V_FA_LENGTHS: the find-all kernel's plain layout,
+        // V_LENGTHS: the scan kernels' (window addressing); V_FA_TRANSDUCER: the find-all transducer built on it
+        if (!ml67) return false;
+        *out = variant == V_FA_TRANSDUCER ? lower_find_all_transducer(tt, *ml67, cw, max_prog_lds())
+                                          : lower_match_lengths(tt, *ml67, cw, max_prog_lds(), variant == V_FA_LENGTHS);
+        return !out->blob.empty(); // (empty: does not fit the LDS as a plain table -- the ordinary program with backward walks)
+    }
+    *out = lower(tt, (Which)which, cw, variant == V_HBM_TABLE ? 0 : max_prog_lds(), variant == V_WALK, variant == V_BACKMAPS || variant == V_FA_BACKMAPS,
+                 variant == V_FA_PLAIN || variant == V_FA_BACKMAPS);
+    return true;
+}
+
+static int get_program(needle_pattern *p, int which, int cw, Variant variant, const DevProgram **out, int *n_cus) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    // cw = 1 | page << 8: the BYTE program of the pattern rebased to one page of the BMP (UTF-16 rows narrowed on the fly: utf16_route)
+    const int page = cw >> 8, cw_key = cw;
+    cw &= 0xFF;
+    const bool wants_ml = variant_wants_ml(p, which, variant);
+    const MatchLengths *ml67 = wants_ml ? pattern_ml(p) : nullptr; // (before p->mu: see ml_mu)
+    std::lock_guard<std::mutex> lk(p->mu);
+    const RefTables *tt = tables_for_page(p, page, &ml67);
     if (!p->cus.count(dev)) {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, dev));
@@ -253,42 +293,10 @@ static int get_program(needle_pattern *p, int which, int cw, Variant variant, co
     auto it = p->cache.find(key);
     if (it == p->cache.end()) {
         DevProgram dp;
-        if (variant == V_FILTER_HBM || variant == V_FILTER_WIDE || variant == V_FILTER_UNBOUNDED) {
-            if ((wants_ml && !ml67) || (variant == V_FILTER_WIDE && cw != 2) || (variant == V_FILTER_UNBOUNDED && (which != W_FORWARDS || cw != 1))) {
-                *out = nullptr;
-                return NEEDLE_OK;
-            }
-            dp.prog = variant == V_FILTER_WIDE ? lower_filter_wide(*tt, (Which)which, ml67)
-                                               : lower_filter_hbm(*tt, (Which)which, variant == V_FILTER_UNBOUNDED ? nullptr : ml67, variant == V_FILTER_UNBOUNDED);
-            if (dp.prog.blob.empty() || !dp.prog.ng.p.on) { // (no filter: the ordinary program is what runs)
-                p->cache.emplace(key, DevProgram());
-                *out = nullptr;
-                return NEEDLE_OK;
-            }
-        } else if (variant == V_FA_RUNS) { // (absent when the pattern is not one of runs)
-            dp.prog = lower_find_all_runs(*tt, cw, max_prog_lds());
-            if (dp.prog.blob.empty()) {
-                p->cache.emplace(key, DevProgram());
-                *out = nullptr;
-                return NEEDLE_OK;
-            }
-        } else if (variant == V_FA_LENGTHS || variant == V_LENGTHS || variant == V_FA_TRANSDUCER) {
-            // "lengths" form: the refined forward automaton + pend[] (needle_lower.h); V_FA_LENGTHS: the find-all kernel's plain layout,
-            // V_LENGTHS: the scan kernels' (window addressing); V_FA_TRANSDUCER: the find-all transducer built on it
-            if (!ml67) {
-                *out = nullptr;
-                return NEEDLE_OK;
-            }
-            dp.prog = variant == V_FA_TRANSDUCER ? lower_find_all_transducer(*tt, *ml67, cw, max_prog_lds())
-                                                 : lower_match_lengths(*tt, *ml67, cw, max_prog_lds(), variant == V_FA_LENGTHS);
-            if (dp.prog.blob.empty()) { // (does not fit the LDS as a plain table: the ordinary program with backward walks)
-                p->cache.emplace(key, DevProgram());
-                *out = nullptr;
-                return NEEDLE_OK;
-            }
-        } else {
-            dp.prog = lower(*tt, (Which)which, cw, variant == V_HBM_TABLE ? 0 : max_prog_lds(), variant == V_WALK, variant == V_BACKMAPS || variant == V_FA_BACKMAPS,
-                            variant == V_FA_PLAIN || variant == V_FA_BACKMAPS);
+        if (!lower_variant(*tt, which, cw, variant, wants_ml, ml67, &dp.prog)) { // (an empty entry = "not available for this pattern / width")
+            p->cache.emplace(key, DevProgram());
+            *out = nullptr;
+            return NEEDLE_OK;
         }
         HIP_TRY(hipMalloc((void **)&dp.d_blob, dp.prog.blob.size()));
         if (hipError_t ce = hipMemcpy(dp.d_blob, dp.prog.blob.data(), dp.prog.blob.size(), hipMemcpyHostToDevice); ce != hipSuccess) {
@@ -1109,6 +1117,63 @@ static int find_all_lane_program(needle_pattern *p, int cw, bool count_only, Lan
     return NEEDLE_OK;
 }
 
+// The program the n-gram filter kernel's FIND-ALL form runs on for this pattern on rows of cw (needle_ngram.hip OP_NG_FIND_ALL; packed rows:
+// needle_ngram_packed.h) -- one choice for both layouts.  As find() chooses its filter: the 8-bit program find() walks (plain table for a
+// pattern of one length, else the lengths form) where it carries a filter, else the filter with its walks out of HBM / L2; UTF-16 rows of a
+// pattern on one page of the BMP: that page's byte programs, the text narrowed as it is loaded (utf16_route); on several pages: the WIDE
+// filter where find() would take it (choose_route, route 3).  Asked through `get`, which answers with a variant's program at char width
+// cw | page << 8 (nullptr: the pattern has none): get_program on a device, a host-side lowering for
+// needle_pattern_find_all_packed_filter.  c->prog == nullptr: no filter for this pattern.  NEEDLE_FIND_ALL_FILTER=0: off (A/B, tests).
+struct FilterChoice {
+    const Program *prog = nullptr;
+    Variant variant = V_PLAIN;
+    int cw_key = 1;          // the program's char width | page << 8
+    int page = 0, sub = 0xFF; // what the launchers are told about UTF-16 rows behind a byte program
+};
+template <class Get>
+static int find_all_filter_choice(const needle_pattern *p, int cw, Get &&get, FilterChoice *c) {
+    *c = FilterChoice();
+    static const bool fa_filter = (getenv("NEEDLE_FIND_ALL_FILTER") ? atoi(getenv("NEEDLE_FIND_ALL_FILTER")) : 1) != 0;
+    if (!fa_filter || ngram_level() <= 0 || !(p->t.fixed_len >= 0 || find_lengths_for(MODE_SPARSE))) return NEEDLE_OK;
+    // (UTF-16 rows of a pattern on one page of the BMP: that page's byte programs, the text narrowed as it is loaded -- utf16_route)
+    const Utf16Route u16 = cw == 2 ? utf16_route(p) : Utf16Route();
+    int rc = NEEDLE_OK;
+    const Program *sp = nullptr;
+    if (cw == 2 && u16.page < 0) { // several pages of the BMP: the WIDE filter, where find() would take it (choose_route, route 3)
+        const Program *op16 = nullptr;
+        if ((rc = get(2, p->t.fixed_len < 0 ? V_BACKMAPS : V_PLAIN, &op16))) return rc;
+        if (op16 && wide_filter_wanted(op16->hdr.mode)) {
+            c->cw_key = 2, c->variant = V_FILTER_WIDE;
+            if ((rc = get(c->cw_key, c->variant, &sp))) return rc;
+        }
+    } else {
+        c->cw_key = 1 | ((cw == 2 ? u16.page : 0) << 8);
+        c->variant = p->t.fixed_len >= 0 ? V_PLAIN : V_LENGTHS;
+        if ((rc = get(c->cw_key, c->variant, &sp))) return rc;
+        if (!(sp && sp->ng.p.on)) { // an automaton that fits the LDS in no form: the filter with its walks out of HBM / L2
+            c->variant = V_FILTER_HBM;
+            if ((rc = get(c->cw_key, c->variant, &sp))) return rc;
+        }
+    }
+    if (sp && sp->ng.p.on) c->prog = sp;
+    c->page = u16.page > 0 ? u16.page : 0, c->sub = cw == 2 ? u16.sub : 0xFF;
+    return NEEDLE_OK;
+}
+// The choice on the current device: the resident program (nullptr: no filter).
+static int find_all_filter_program(needle_pattern *p, int cw, FilterChoice *c, const DevProgram **sp, int *n_cus) {
+    *sp = nullptr;
+    int rc = find_all_filter_choice(p, cw, [&](int cw_key, Variant v, const Program **pr) {
+        const DevProgram *dp = nullptr;
+        const int r = get_program(p, W_FORWARDS, cw_key, v, &dp, n_cus);
+        *pr = (r == NEEDLE_OK && dp) ? &dp->prog : nullptr;
+        return r;
+    }, c);
+    if (rc || !c->prog) return rc;
+    if ((rc = get_program(p, W_FORWARDS, c->cw_key, c->variant, sp, n_cus))) return rc; // (resident by now)
+    if (*sp && !(*sp)->d_ng) *sp = nullptr;
+    return NEEDLE_OK;
+}
+
 // The "more" flag of a one-pass find-all launch: a zeroed scratch word the kernel sets when some row has a match beyond its last slot.
 // launch(d_more) enqueues the kernel (and what belongs behind it); the flag is read back -- the call's only synchronisation -- only when the
 // caller asked whether its slots sufficed (more != nullptr).
@@ -1722,6 +1787,62 @@ static int packed_find_all_by_conversion(needle_pattern *p, const needle_packed_
     return done(NEEDLE_OK);
 }
 
+// Big dictionaries -- no transducer, a program the per-lane kernel does not take (compressed, hot rows, HBM table) -- behind the n-gram
+// candidate filter's find-all form on the packed text itself (needle_ngram_packed.h): one stream-ordered launch, no offsets read-back, no
+// chunks, rows of any length.  The filter program is the fixed-stride rows' (find_all_filter_choice); what is this layout's own:
+//   NEEDLE_PREFILTER_PACKED=0 (no filter in front of packed rows at all) and NEEDLE_FIND_ALL_FILTER_PACKED=0 (this route only; A/B, tests),
+//   no shape gate -- the kernel is right for any amount of text -- but the modes it is instantiated for, a one-length pattern of at most
+//   65 535 chars (the candidate entry's fields) and its own LDS footprint.
+// The two predicates below are what the routing and needle_pattern_find_all_packed_filter both ask.
+static bool packed_find_all_filter_on() {
+    static const bool on = (getenv("NEEDLE_PREFILTER_PACKED") ? atoi(getenv("NEEDLE_PREFILTER_PACKED")) : 1) != 0 &&
+                           (getenv("NEEDLE_FIND_ALL_FILTER_PACKED") ? atoi(getenv("NEEDLE_FIND_ALL_FILTER_PACKED")) : 1) != 0;
+    return on;
+}
+static bool packed_find_all_filter_takes(const needle_pattern *p, const Program &pr) {
+    const uint32_t m = pr.hdr.mode;
+    if (m != MODE_TABLE8 && m != MODE_TABLE16 && m != MODE_SPARSE && m != MODE_GLOBAL) return false;
+    if (p->t.fixed_len > 65535) return false;
+    return pr.ng.p.on && ngram_packed_find_all_lds_bytes(pr.hdr, pr.ng.p) != 0;
+}
+// *taken = false: the batch goes by conversion (no filter program, or the flood watch / the pin declined this call).
+static int packed_find_all_filter(needle_pattern *p, const needle_packed_view *v, uint32_t *d_counts, const uint64_t *d_offsets, int32_t *d_start,
+                                  int32_t *d_end, bool count_only, int *more, hipStream_t stream, bool *taken) {
+    *taken = false;
+    if (!packed_find_all_filter_on()) return NEEDLE_OK;
+    const int cw = (int)v->char_width;
+    FilterChoice fc;
+    const DevProgram *sp = nullptr;
+    int cus = 0;
+    int rc = find_all_filter_program(p, cw, &fc, &sp, &cus);
+    if (rc) return rc;
+    if (!sp || !packed_find_all_filter_takes(p, sp->prog) || !ngram_watch_allows(p, sp)) return NEEDLE_OK; // (the flood watch LAST: it counts the call)
+    *taken = true;
+    const ScanArgs a = scan_args(v, sp, nullptr, p->t.fixed_len, ScanOut());
+    return with_more_flag(stream, more, "find_all (packed filter kernel)", [&](int32_t *d_more) {
+        hipError_t e = launch_ngram_packed_find_all(a, v->offsets, sp->prog.ng.p, sp->d_ng, sp->d_ng_stats, d_counts, d_start, d_end, d_more, d_offsets, count_only,
+                                                    cus, stream, cw, fc.page, fc.sub);
+        if (e == hipSuccess) e = ngram_watch_after_launch(sp, stream);
+        return e;
+    });
+}
+
+// The packed find-all entries' route: the transducer kernel, else the per-lane kernel, else the filter kernel, else conversion.
+static int packed_find_all_route(needle_pattern *p, const needle_packed_view *v, uint32_t *d_counts, const uint64_t *d_offsets, int32_t *d_start,
+                                 int32_t *d_end, bool count_only, int *more, hipStream_t stream) {
+    const DevProgram *tp = nullptr;
+    int n_cus = 0;
+    int rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
+    if (rc) return rc;
+    if (tp) return packed_find_all_launch(v, tp, n_cus, d_counts, d_offsets, d_start, d_end, 0, nullptr, count_only, more, nullptr, stream);
+    bool taken = false;
+    rc = packed_find_all_lane(p, v, d_counts, d_offsets, d_start, d_end, count_only, more, stream, &taken);
+    if (rc || taken) return rc;
+    rc = packed_find_all_filter(p, v, d_counts, d_offsets, d_start, d_end, count_only, more, stream, &taken);
+    if (rc || taken) return rc;
+    return packed_find_all_by_conversion(p, v, d_counts, d_offsets, d_start, d_end, more, stream);
+}
+
 extern "C" {
 
 int needle_count_matches_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t *d_counts, void *stream_) {
@@ -1730,15 +1851,7 @@ int needle_count_matches_packed_dev(const needle_pattern *cp, const needle_packe
     if (rc) return rc;
     if (!d_counts) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
     if (v->n_rows == 0) return NEEDLE_OK;
-    const DevProgram *tp = nullptr;
-    int n_cus = 0;
-    rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
-    if (rc) return rc;
-    if (tp) return packed_find_all_launch(v, tp, n_cus, d_counts, nullptr, nullptr, nullptr, 0, nullptr, true, nullptr, nullptr, (hipStream_t)stream_);
-    bool taken = false;
-    rc = packed_find_all_lane(p, v, d_counts, nullptr, nullptr, nullptr, true, nullptr, (hipStream_t)stream_, &taken);
-    if (rc || taken) return rc;
-    return packed_find_all_by_conversion(p, v, d_counts, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+    return packed_find_all_route(p, v, d_counts, nullptr, nullptr, nullptr, true, nullptr, (hipStream_t)stream_);
 }
 
 int needle_find_all_csr_packed_dev(const needle_pattern *cp, const needle_packed_view *v, const uint64_t *d_offsets, int32_t *d_start,
@@ -1749,15 +1862,7 @@ int needle_find_all_csr_packed_dev(const needle_pattern *cp, const needle_packed
     if (!d_offsets || !d_start || !d_end) return fail(NEEDLE_ERR_INVALID, "offsets / output buffer is NULL");
     if (more) *more = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
-    const DevProgram *tp = nullptr;
-    int n_cus = 0;
-    rc = packed_find_all_program(p, (int)v->char_width, &tp, &n_cus);
-    if (rc) return rc;
-    if (tp) return packed_find_all_launch(v, tp, n_cus, nullptr, d_offsets, d_start, d_end, 0, nullptr, false, more, nullptr, (hipStream_t)stream_);
-    bool taken = false;
-    rc = packed_find_all_lane(p, v, nullptr, d_offsets, d_start, d_end, false, more, (hipStream_t)stream_, &taken);
-    if (rc || taken) return rc;
-    return packed_find_all_by_conversion(p, v, nullptr, d_offsets, d_start, d_end, more, (hipStream_t)stream_);
+    return packed_find_all_route(p, v, nullptr, d_offsets, d_start, d_end, false, more, (hipStream_t)stream_);
 }
 
 int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t max_per_row, uint64_t *d_offsets,
@@ -2299,7 +2404,8 @@ int needle_pattern_find_all_transducer(const needle_pattern *cp, int char_width,
 }
 
 // Which route needle_count_matches_packed_dev (count_only) / needle_find_all_csr_packed_dev take for this pattern on rows of char_width:
-// 0 conversion, 1 the transducer kernel, 2 the per-lane kernel.  Answers without a device: the programs are lowered on the host, the
+// 0 neither the transducer nor the per-lane kernel (the filter kernel where needle_pattern_find_all_packed_filter says so, else
+// conversion), 1 the transducer kernel, 2 the per-lane kernel.  Answers without a device: the programs are lowered on the host, the
 // questions are the entries' own (packed_find_all_takes by way of needle_pattern_find_all_transducer, find_all_lane_choice,
 // packed_find_all_lane_takes).
 int needle_pattern_find_all_packed_route(const needle_pattern *cp, int char_width, int count_only, int32_t *route) {
@@ -2328,6 +2434,37 @@ int needle_pattern_find_all_packed_route(const needle_pattern *cp, int char_widt
     }, &c);
     if (rc) return rc;
     if (packed_find_all_lane_takes(*c.hdr, char_width)) *route = 2;
+    return NEEDLE_OK;
+}
+
+// Whether the packed find-all entries take the FILTER kernel for this pattern on rows of char_width (needle_ngram_packed.h): neither the
+// transducer nor the per-lane kernel takes it (needle_pattern_find_all_packed_route says 0) and the filter's find-all form has a program
+// for it.  Answers without a device, with the routing's own predicates (packed_find_all_filter_on, find_all_filter_choice on host-side
+// lowerings, packed_find_all_filter_takes); the flood watch and the needle_pattern_set_prefilter pin are runtime state and left aside.
+int needle_pattern_find_all_packed_filter(const needle_pattern *cp, int char_width, int count_only, int32_t *available) {
+    if (!cp || !available || (char_width != 1 && char_width != 2) || (count_only != 0 && count_only != 1)) return fail(NEEDLE_ERR_INVALID, "bad argument");
+    *available = 0;
+    int32_t route = 0;
+    int rc = needle_pattern_find_all_packed_route(cp, char_width, count_only, &route);
+    if (rc || route != 0 || !packed_find_all_filter_on()) return rc;
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    std::vector<std::unique_ptr<Program>> lowered; // (the choice holds pointers into it)
+    FilterChoice fc;
+    rc = find_all_filter_choice(cp, char_width, [&](int cw_key, Variant v, const Program **pr) {
+        *pr = nullptr;
+        const bool wants_ml = variant_wants_ml(cp, W_FORWARDS, v);
+        const MatchLengths *ml = wants_ml ? pattern_ml(cp) : nullptr; // (before p->mu: see ml_mu)
+        std::lock_guard<std::mutex> lk(p->mu);
+        const RefTables *tt = tables_for_page(p, cw_key >> 8, &ml);
+        std::unique_ptr<Program> out(new Program());
+        if (lower_variant(*tt, W_FORWARDS, cw_key & 0xFF, v, wants_ml, ml, out.get())) {
+            *pr = out.get();
+            lowered.push_back(std::move(out));
+        }
+        return (int)NEEDLE_OK;
+    }, &fc);
+    if (rc) return rc;
+    if (fc.prog && packed_find_all_filter_takes(cp, *fc.prog)) *available = 1;
     return NEEDLE_OK;
 }
 
@@ -2516,37 +2653,19 @@ static int find_all_one_pass(needle_pattern *p, const needle_batch_view *v, uint
     fa.packed = d_packed;
     // Dictionaries whose find() runs behind the n-gram candidate filter (needle_ngram.hip): their find-all does too -- the filter
     // kernel's find-all form files every verified candidate and each row sorts its own out against its moving cursor (dense slots,
-    // the counting pass and the compact filing alike).  NEEDLE_FIND_ALL_FILTER=0: off (A/B, tests).
-    static const bool fa_filter = (getenv("NEEDLE_FIND_ALL_FILTER") ? atoi(getenv("NEEDLE_FIND_ALL_FILTER")) : 1) != 0;
-    // (UTF-16 rows of a pattern on one page of the BMP: that page's byte programs, the text narrowed as it is loaded -- utf16_route)
-    const Utf16Route u16 = cw == 2 ? utf16_route(p) : Utf16Route();
-    if (fa_filter && (count_only || d_offsets || slots) && ngram_level() > 0 && (p->t.fixed_len >= 0 || find_lengths_for(MODE_SPARSE))) {
+    // the counting pass and the compact filing alike).  The program: find_all_filter_choice.
+    if (count_only || d_offsets || slots) {
+        FilterChoice fc;
         const DevProgram *sp = nullptr;
         int cus = 0;
-        if (cw == 2 && u16.page < 0) { // several pages of the BMP: the WIDE filter, where find() would take it (choose_route, route 3)
-            const DevProgram *op16 = nullptr;
-            rc = get_program(p, W_FORWARDS, 2, p->t.fixed_len < 0 ? V_BACKMAPS : V_PLAIN, &op16, &cus);
-            if (rc) return rc;
-            if (op16 && wide_filter_wanted(op16->prog.hdr.mode)) {
-                rc = get_program(p, W_FORWARDS, 2, V_FILTER_WIDE, &sp, &cus);
-                if (rc) return rc;
-            }
-        } else {
-            const int cw8 = 1 | ((cw == 2 ? u16.page : 0) << 8);
-            rc = get_program(p, W_FORWARDS, cw8, p->t.fixed_len >= 0 ? V_PLAIN : V_LENGTHS, &sp, &cus);
-            if (rc) return rc;
-            if (!(sp && sp->d_ng && sp->prog.ng.p.on)) { // an automaton that fits the LDS in no form: the filter with its walks out of HBM / L2
-                rc = get_program(p, W_FORWARDS, cw8, V_FILTER_HBM, &sp, &cus);
-                if (rc) return rc;
-            }
-        }
-        if (sp && sp->d_ng && sp->prog.ng.p.on && ngram_find_all_lds_bytes(sp->prog.hdr, sp->prog.ng.p)) {
+        if ((rc = find_all_filter_program(p, cw, &fc, &sp, &cus))) return rc;
+        if (sp && ngram_find_all_lds_bytes(sp->prog.hdr, sp->prog.ng.p)) {
             // (UTF-16 rows: the stride in CHARS -- launch_ngram_find_all with char_width 2)
             const ScanArgs a = scan_args(v, v->row_stride, sp, nullptr, p->t.fixed_len, ScanOut());
             if (ngram_shape_ok(a) && ngram_watch_allows(p, sp))
                 return with_more_flag(stream, more, "find_all (filter kernel)", [&](int32_t *d_more) {
                     hipError_t e = launch_ngram_find_all(a, sp->prog.ng.p, sp->d_ng, sp->d_ng_stats, slots, d_counts, d_start, d_end, d_packed, d_more, d_offsets,
-                                                         count_only, cus, stream, cw, u16.page > 0 ? u16.page : 0, cw == 2 ? u16.sub : 0xFF, kshift);
+                                                         count_only, cus, stream, cw, fc.page, fc.sub, kshift);
                     if (e == hipSuccess) e = ngram_watch_after_launch(sp, stream);
                     return e;
                 });

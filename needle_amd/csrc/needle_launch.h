@@ -57,6 +57,11 @@ hipError_t launch_ngram_find_all(const ScanArgs &a, const NgramParams &ng, const
 size_t ngram_packed_lds_bytes(const ProgHeader &h, const NgramParams &ng);
 hipError_t launch_ngram_packed(int op, const ScanArgs &a, const uint64_t *offsets, int32_t *overflow, const NgramParams &ng, const uint32_t *d_bitmap,
                                uint32_t *d_stats, int n_cus, hipStream_t stream, int char_width, int page, int sub);
+// needle_ngram_packed_find_all2.hip: ... and its find-all form (counting, or compact filing at the caller's offsets)
+size_t ngram_packed_find_all_lds_bytes(const ProgHeader &h, const NgramParams &ng);
+hipError_t launch_ngram_packed_find_all(const ScanArgs &a, const uint64_t *row_offsets, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats,
+                                        uint32_t *counts, int32_t *starts, int32_t *ends, int32_t *more, const uint64_t *offsets, bool count_only, int n_cus,
+                                        hipStream_t stream, int char_width, int page, int sub);
 // needle_lower.cpp (NEEDLE_PREFILTER)
 int ngram_level();
 

@@ -54,6 +54,10 @@ constexpr uint32_t kNgRowSlots = 2;
 constexpr uint32_t kNgWaveLdsFA = kNgQueue * 4 + 64 * kNgRowSlots * 8 + 64 * 4;
 // ... of its packed-rows form (needle_ngram_packed.h): the two queues, the slots and the group's 65 row starts (64 rows + the end)
 constexpr uint32_t kNgWaveLdsPacked = kNgWaveLds + 272;
+// ... of the find-all form on packed rows: the find-all form's queue, slots and counters + the group's 64 row starts (the second level's
+// queue comes on top, as for kNgWaveLdsFA).  64, not 65: the position behind the last row is the group's end, which the wave holds in a
+// register anyway -- with a 65th entry (272 bytes) a 96 KB compressed automaton, its 32 KB bitmap and 16 waves miss the 160 KB by 256 bytes
+constexpr uint32_t kNgWaveLdsPackedFA = kNgWaveLdsFA + 256;
 constexpr uint32_t kNgWaves = 16;
 constexpr uint32_t kNgLdsCap = 160u * 1024u;
 

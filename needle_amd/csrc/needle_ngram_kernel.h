@@ -66,7 +66,7 @@ typedef __attribute__((address_space(3))) uint64_t lds_u64_t;
 // filter, and the two cases that are walked row by row instead (spans beyond 32-bit stream positions, batches below 16 chars).
 template <int OP, int MODE, int S, int CW, bool WIDE, bool BWD, bool PACKED>
 __device__ __forceinline__ void ngram_body(const NgramArgs A) {
-    static_assert(!PACKED || (OP != 3 && !BWD), "packed rows: containedIn() and find() with bounded match lengths");
+    static_assert(!PACKED || !BWD, "packed rows: containedIn(), find() and find-all with bounded match lengths");
     static_assert(!WIDE || (CW == 2 && MODE == MODE_GLOBAL), "the wide filter verifies on the UTF-16 HBM-table program");
     static_assert(!BWD || (OP == OP_FIND && CW == 1 && !WIDE), "backward walks: find() on 8-bit rows");
     constexpr int TW = WIDE ? 2 : 1; // width of the code units the probes and the walks see
@@ -106,7 +106,7 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
     wk.gtable = MODE == MODE_GLOBAL ? (const uint16_t *)(a.prog + a.hdr.off_table) : nullptr;
     wk.hot_last = 0;
     const uint32_t accept_lo = a.hdr.accept_lo, start_state = a.hdr.start;
-    const uint32_t qbase = A.lay.q_base + (uint32_t)wave * (FA ? kNgWaveLdsFA + (A.ng.on2 ? kNgQueue * 4u : 0u) : PACKED ? kNgWaveLdsPacked : kNgWaveLds);
+    const uint32_t qbase = A.lay.q_base + (uint32_t)wave * (FA ? (PACKED ? kNgWaveLdsPackedFA : kNgWaveLdsFA) + (A.ng.on2 ? kNgQueue * 4u : 0u) : PACKED ? kNgWaveLdsPacked : kNgWaveLds);
     const uint32_t q2base = qbase + kNgQueue * 4u; // find / containedIn: the second queue (candidates that passed the second-level window)
     const uint32_t sbase = qbase + ((FA && !A.ng.on2) ? 1u : 2u) * kNgQueue * 4u; // find / containedIn: the rows' slots; find-all: two candidate slots per row ...
     const uint32_t cbase = sbase + 64u * kNgRowSlots * 8u; // ... and a counter per row
@@ -158,7 +158,7 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
         uint64_t rs;
         uint32_t len;
     };
-    const uint32_t obase = sbase + 64u * 8u; // PACKED: the group's 65 row starts, relative to the stream's base, behind the slots
+    const uint32_t obase = FA ? cbase + 64u * 4u : sbase + 64u * 8u; // PACKED: the group's 65 row starts, relative to the stream's base, behind the slots (find-all: 64, behind the counters)
     struct PkShape {
         uint64_t base;   // absolute address of the group's stream position 0: its first char's address rounded down to 16 chars
         uint64_t lo;     // the group's first char
@@ -457,8 +457,17 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
             // stays alive for "international" and never sees "nation")
             if (h.found || h.died || h.crossed) {
                 const uint32_t ord = __hip_atomic_fetch_add((lds_u32_t *)(uintptr_t)(cbase + row * 4u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                const uint64_t ent = (uint64_t)qn << 48 | (uint64_t)((h.found && !h.crossed) ? h.first - qn : 0xFFu) << 32 | (uint64_t)(h.last & 0xFFFFu) << 16 |
-                                     (uint64_t)((uint32_t)((int32_t)h.last - h.start) & 0xFFFFu);
+                uint64_t ent = (uint64_t)qn << 48 | (uint64_t)((h.found && !h.crossed) ? h.first - qn : 0xFFu) << 32 | (uint64_t)(h.last & 0xFFFFu) << 16 |
+                               (uint64_t)((uint32_t)((int32_t)h.last - h.start) & 0xFFFFu);
+                if constexpr (PACKED) {
+                    // rows of any length: the window's end as 32 bits on top (the order by window end survives), first - qn (8 bits, 0xFF:
+                    // unknown), then what the pattern bounds -- one length: last - qn (24 bits; the length is a.fixed_len, at most 65 535:
+                    // the host checks); a lengths program: last - qn (16 bits) and the match length (8: pend[] is bytes)
+                    const KernargPtr ka = kernarg_here();
+                    const uint32_t dl = h.last - qn, ml = (uint32_t)((int32_t)h.last - h.start);
+                    const uint32_t low = (int32_t)NEEDLE_NG_U32(a.fixed_len) >= 0 ? dl & 0xFFFFFFu : (dl & 0xFFFFu) << 8 | (ml & 0xFFu);
+                    ent = (uint64_t)qn << 32 | (uint64_t)((h.found && !h.crossed) ? h.first - qn : 0xFFu) << 24 | (uint64_t)low;
+                }
                 if (ord < kNgRowSlots) *(lds_u64_t *)(uintptr_t)(sbase + (row * kNgRowSlots + ord) * 8u) = ent;
             }
         } else if (OP == OP_FIND) {
@@ -488,7 +497,14 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
                 const uint32_t v = *(const lds_u32_t *)(uintptr_t)(obase + (lo + step) * 4u);
                 lo = v <= em1 ? lo + step : lo;
             }
-            const uint32_t rs = *(const lds_u32_t *)(uintptr_t)(obase + lo * 4u), re = *(const lds_u32_t *)(uintptr_t)(obase + lo * 4u + 4u);
+            const uint32_t rs = *(const lds_u32_t *)(uintptr_t)(obase + lo * 4u);
+            uint32_t re;
+            if constexpr (FA) { // (the find-all form keeps the 64 starts only -- kNgWaveLdsPackedFA: the position behind the last row is the group's end)
+                const uint32_t nx = *(const lds_u32_t *)(uintptr_t)(obase + (lo < 63u ? lo + 1u : 63u) * 4u);
+                re = lo < 63u ? nx : cur_sh.end;
+            } else {
+                re = *(const lds_u32_t *)(uintptr_t)(obase + lo * 4u + 4u);
+            }
             const bool in = rs <= em1 && em1 < re;
             row = in ? lo : 64u;
             qn = in ? e - rs : 0u;
@@ -559,7 +575,7 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
         if constexpr (PACKED) { // the rows' starts as stream positions, and the position behind the last row
             if (!cur_sh.direct) {
                 *(lds_u32_t *)(uintptr_t)(obase + (uint32_t)lane * 4u) = cur_sh.lead + (uint32_t)(cur_o0 - cur_sh.lo);
-                if (lane == 63) *(lds_u32_t *)(uintptr_t)(obase + 64u * 4u) = cur_sh.end;
+                if (!FA && lane == 63) *(lds_u32_t *)(uintptr_t)(obase + 64u * 4u) = cur_sh.end;
             }
             asm volatile("" ::: "memory");
         }
@@ -693,7 +709,14 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
                 const uint64_t t = e0;
                 e0 = e1, e1 = t;
             }
-            bool slow = row_ok && n_mine > kNgRowSlots;
+            // (PACKED: a direct group saw no filter -- every row is searched match by match from char 0)
+            bool slow = row_ok && (n_mine > kNgRowSlots || (PACKED && cur_sh.direct));
+            const RowRef own{cur_o0, (uint32_t)(cur_o1 - cur_o0)}; // (PACKED: the lane's own row, for the walks below)
+            int32_t fixed_len = -1;
+            if constexpr (PACKED) {
+                const KernargPtr ka = kernarg_here();
+                fixed_len = (int32_t)NEEDLE_NG_U32(a.fixed_len);
+            }
             uint32_t cursor = 0, cnt = 0;
             bool more_f = false;
             uint64_t out0 = A.fa_kshift ? g * (uint64_t)A.fa_slots * 64u + (uint64_t)lane : ((g << 6) + lane) * (uint64_t)A.fa_slots;
@@ -707,7 +730,7 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
                 more_f = more_f || (hit && !file);
                 if (file && !A.fa_count_only) {
                     const uint64_t o = out0 + ((uint64_t)cnt << (A.fa_offsets ? 0u : A.fa_kshift));
-                    if (A.fa_packed) {
+                    if (!PACKED && A.fa_packed) { // (packed rows: counting and compact filing only)
                         A.fa_packed[o] = (uint32_t)start | (last << 16);
                     } else {
                         A.fa_starts[o] = start;
@@ -722,14 +745,21 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
                 const uint64_t x = e0;
                 e0 = e1, e1 = ~0ull;
                 const bool have = row_ok && !slow && !more_f && x != ~0ull;
-                const uint32_t e = (uint32_t)(x >> 48), last = (uint32_t)((x >> 16) & 0xFFFFu), mlen = (uint32_t)(x & 0xFFFFu);
-                const bool unknown = ((x >> 32) & 0xFFu) == 0xFFu;
+                uint32_t e = (uint32_t)(x >> 48), last = (uint32_t)((x >> 16) & 0xFFFFu), mlen = (uint32_t)(x & 0xFFFFu);
+                bool unknown = ((x >> 32) & 0xFFu) == 0xFFu;
+                if constexpr (PACKED) { // (the wide entry of run_rows)
+                    const uint32_t low = (uint32_t)x & 0xFFFFFFu;
+                    e = (uint32_t)(x >> 32);
+                    last = e + (fixed_len >= 0 ? low : low >> 8);
+                    mlen = fixed_len >= 0 ? (uint32_t)fixed_len : low & 0xFFu;
+                    unknown = (((uint32_t)x >> 24) & 0xFFu) == 0xFFu;
+                }
                 const uint32_t r0 = e > K ? e - K : 0u;
                 const bool exact = have && !unknown && r0 >= cursor;
                 const bool again = have && !exact && e + (uint32_t)S - 1u > cursor;
                 Hit h2;
                 h2.found = false, h2.died = false, h2.crossed = false, h2.first = 0, h2.last = 0, h2.start = 0;
-                if (__ballot(again) != 0ull) h2 = walk_row(g, (uint32_t)lane, again, e > cursor ? e : cursor + 1u, cursor, e + (uint32_t)S - 1u);
+                if (__ballot(again) != 0ull) h2 = walk_row(g, (uint32_t)lane, again, e > cursor ? e : cursor + 1u, cursor, e + (uint32_t)S - 1u, own);
                 // (a re-run from the cursor IS the reference's search; should it accept before this window -- a match whose own window
                 // was never filed -- the row is searched match by match below: exact whatever the filter missed)
                 const bool lost = again && h2.crossed;
@@ -738,7 +768,7 @@ __device__ __forceinline__ void ngram_body(const NgramArgs A) {
             }
             while (__ballot(slow && !more_f) != 0ull) { // the reference's loop, one find() at a time, for the rows that need it
                 const bool todo = slow && !more_f;
-                const Hit h = walk_row(g, (uint32_t)lane, todo, cursor, cursor, 0xFFFFFFFFu);
+                const Hit h = walk_row(g, (uint32_t)lane, todo, cursor, cursor, 0xFFFFFFFFu, own);
                 emit(todo && h.found, h.last, h.start);
                 slow = todo && h.found && !more_f;
             }

@@ -45,8 +45,15 @@
 // Served: containedIn() and find() with a lengths form or a fixed length -- 8-bit rows on LDS programs (table8, table16, compressed)
 // and on walks out of HBM (MODE_GLOBAL), UTF-16 rows of one-page patterns (byte program of the page, narrowed on load) and of
 // multi-page patterns (WIDE) -- with int32 pairs or the one-word forms (pack16_or_over / pack8_or_over + overflow flag).
+// Find-all (OP_NG_FIND_ALL, needle_ngram_packed_find_all{1,2}.hip; count / CSR entries of big dictionaries): stream, offsets, candidate
+// location and direct groups as above; filing and the group's end are the fixed-stride find-all form's (needle_ngram_kernel.h run_rows:
+// two slots + a counter per row, lane = row sorts its candidates against its moving cursor, re-runs a window from the cursor, falls to
+// the match-by-match loop).  The filed entry is 64 bits for rows of any length: window end (32, on top) | first - end (8, 0xFF: unknown) |
+// 24 bits bounded by the pattern -- one length: last - end; a lengths program: last - end (16) and the match length (8).  A direct group
+// runs the match-by-match loop on every row from char 0.  LDS per wave: kNgWaveLdsPackedFA (64 row starts: the position behind the last
+// row is the group's end, held in a register).
 // NOT served, these keep the plain packed kernels: matches() (the filter never serves it), per-row cursors
-// (needle_find_next_packed_dev), find-all of packed rows, find() of patterns without bounded match lengths (the fixed-stride variant
+// (needle_find_next_packed_dev), find() of patterns without bounded match lengths (the fixed-stride variant
 // 12 with backward walks has no packed form), and the *_packed_host entries' routing is unchanged.
 #pragma once
 #include "needle_ngram_kernel.h"

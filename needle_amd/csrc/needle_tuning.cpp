@@ -29,6 +29,7 @@ const Switch kSwitches[] = {
     {"NEEDLE_FIND_ALL_LENGTHS", "1", "layout", "find-all's starts: 0 by backward walks, 1 by the lengths automaton where it fits the LDS as a plain table, 2 also in its compressed form (big dictionaries; measured: no faster)"},
     {"NEEDLE_FIND_ALL_LOCKSTEP", "1", "layout", "0: find-all never takes the lock-step kernel (the find-all transducer, needle_find_all_ls.hip); patterns that have one keep the per-lane one-pass kernel"},
     {"NEEDLE_FIND_ALL_RUNS", "1", "layout", "0: find-all of run patterns (`[0-9]+`: no bounded match length) never takes the lock-step kernel with the run transducer; they keep the per-lane one-pass kernel and its backward walks"},
+    {"NEEDLE_FIND_ALL_FILTER_PACKED", "1", "layout", "0: packed find-all (needle_count_matches_packed_dev / needle_find_all_csr_packed_dev) of big dictionaries (compressed, hot-rows, HBM-table programs) never takes the n-gram filter kernel's find-all form on the packed text (needle_ngram_packed.h); they go by conversion to fixed-stride rows (offsets read back, chunked; for A/B runs).  NEEDLE_PREFILTER_PACKED=0 switches that route off too"},
     {"NEEDLE_PACKED_FIND_ALL_LANE", "1", "layout", "0: packed find-all (needle_count_matches_packed_dev / needle_find_all_csr_packed_dev) of patterns without a find-all transducer never takes the packed per-lane kernel (needle_packed_find_all_lane.h); they go by conversion to fixed-stride rows (offsets read back, chunked; for A/B runs)"},
     {"NEEDLE_FIND_ALL_FILTER", "1", "layout", "0: find-all never runs behind the n-gram candidate filter (dictionaries whose find() does keep the one-pass find-all kernel)"},
     {"NEEDLE_FIND_ALL_WINDOW", "1", "layout", "0: the find-all kernel's lengths program keeps column-map lookups instead of window addressing"},

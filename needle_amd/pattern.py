@@ -272,6 +272,14 @@ class Pattern:
         _check(_lib.lib().needle_pattern_find_all_packed_route(self._h, int(char_width), 1 if count_only else 0, ctypes.byref(route)))
         return ("conversion", "transducer", "lane")[route.value]
 
+    def find_all_packed_filter(self, char_width=1, count_only=False):
+        """Whether count_matches_packed (count_only) / find_all_packed take the n-gram filter kernel's find-all form for this pattern on
+        packed device rows of char_width (needle_pattern_find_all_packed_filter; no device needed): neither the transducer nor the
+        per-lane kernel takes it and the filter has a program for it.  The flood watch and set_prefilter are runtime state, left aside."""
+        available = ctypes.c_int32(0)
+        _check(_lib.lib().needle_pattern_find_all_packed_filter(self._h, int(char_width), 1 if count_only else 0, ctypes.byref(available)))
+        return bool(available.value)
+
     def tables(self):
         """The pattern's tables in the reference layout (class map, stride, 4 x (table, accepting, max_char))."""
         inf = self.info()

@@ -19,7 +19,13 @@ and start / end checksums must agree.
   c3np  c3p's text, the dictionary extended by w[:3] and w[3:-1] of the first 100 keywords of at least --nested-min-len chars, longest
         first (a nested dictionary: no transducer -- asserted)
   c2n   c2p's text, the nullable `[0-9]*`
-python scripts/find_all_packed_rate.py [--rows N] [--steps K] [--warmup W] [--only c2p,c3p,c3np,c2n] [--max-per-row M]"""
+Big dictionaries (--only c3sp,c3xp,longp): count + CSR fill through the packed entries on (a) the n-gram filter kernel's find-all form
+(needle_ngram_packed.h) and (b) the conversion route (NEEDLE_FIND_ALL_FILTER_PACKED=0: the route of the commit before the filter route),
+children alternating as above; every child also reports the filter launches (forwards) of its timed steps.
+  c3sp  bench.py's c3s rows (1000 keywords of 6 .. 8 chars: the compressed automaton), lengths uniform in [1, 256], packed
+  c3xp  c3x (3000 keywords: walks out of HBM / L2), the same
+  longp c3s's dictionary over 2000 short rows, one row of 70 000 and one of 200 000 chars (a keyword every ~1400 chars); --rows is ignored
+python scripts/find_all_packed_rate.py [--rows N] [--steps K] [--warmup W] [--only c2p,c3p,c3np,c2n,c3sp,c3xp,longp] [--max-per-row M]"""
 import argparse
 import ctypes
 import json
@@ -34,12 +40,43 @@ os.environ.setdefault("NEEDLE_SCRATCH_KEEP_MB", "16384")
 
 
 LANE_WORKLOADS = ("c3np", "c2n")
+FILTER_WORKLOADS = ("c3sp", "c3xp", "longp")
+# workload -> (the route's switch, what find_all_packed_route / find_all_packed_filter say with the switch on)
+SWITCH = {wl: ("NEEDLE_PACKED_FIND_ALL_LANE", "lane") for wl in LANE_WORKLOADS}
+SWITCH.update({wl: ("NEEDLE_FIND_ALL_FILTER_PACKED", "filter") for wl in FILTER_WORKLOADS})
+
+
+def long_rows_batch(words, dev):
+    """(data, offsets) of the long-row batch: 2000 short rows of c3s's text, a row of 70 000 and one of 200 000 chars among them."""
+    import numpy as np
+    import torch
+    from needle_amd import workload as W
+    rng = np.random.default_rng(17)
+    host = W.keyword_batch(np, words, 0, 2000, 256)
+    lens = np.arange(2000) * 2654435761 % 256 + 1
+    rows = [host[i, :lens[i]] for i in range(2000)]
+    al = np.array([ord(c) for c in "abcdefghijklmnopqrstuvwxyz "], dtype=np.uint8)
+    for at, n in ((777, 70000), (1411, 200000)):
+        r = rng.choice(al, n).astype(np.uint8)
+        for k in range(n // 1400):
+            w = np.array([ord(c) for c in words[k % len(words)]], dtype=np.uint8)
+            r[100 + 1400 * k:100 + 1400 * k + w.size] = w
+        rows.insert(at, r)
+    text = np.concatenate(rows)
+    text = np.concatenate([text, np.zeros((-text.size) % 4, np.uint8)])
+    offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([r.size for r in rows])
+    return torch.from_numpy(text).to(dev), torch.from_numpy(offsets).to(dev)
 
 
 def lane_pattern(wl, nested_min_len):
     """(pattern, label, the base workload whose rows it scans, its planted words)"""
     import bench
     from needle_amd.pattern import DFACompiler
+    if wl in FILTER_WORKLOADS:
+        base = "c3x" if wl == "c3xp" else "c3s"
+        pattern, what, words = bench.make_pattern(base)
+        return pattern, what + (" -- the long-row batch" if wl == "longp" else ", per-row lengths uniform in [1, 256], packed"), base, words
     if wl == "c2n":
         _, _, words = bench.make_pattern("c2")
         return DFACompiler.compile("[0-9]*", "DigitStar"), "'[0-9]*' (nullable) over c2p's text", "c2", words
@@ -63,18 +100,26 @@ def lane_child(args, wl):
     assert pattern.find_all_transducer(1) is None, "%s: the pattern has a transducer" % wl
     route = pattern.find_all_packed_route(1, False)
     assert route == pattern.find_all_packed_route(1, True)
-    lens = (torch.arange(n, device=dev, dtype=torch.int64) * 2654435761 % 256 + 1)
-    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    offsets[1:] = torch.cumsum(lens, 0)
-    col = torch.arange(256, device=dev)[None, :]
-    chars = int(offsets[-1].item())
+    if route == "conversion" and pattern.find_all_packed_filter(1, False):
+        assert pattern.find_all_packed_filter(1, True)
+        route = "filter"
     stream = torch.cuda.current_stream(dev).cuda_stream
-    rows = bench.make_rows(base, words, 0, n, dev)
-    data = torch.empty(chars, dtype=torch.uint8, device=dev)
-    for s in range(0, n, 1 << 20):
-        k = min(1 << 20, n - s)
-        data[int(offsets[s].item()):int(offsets[s + k].item())] = rows[s:s + k][col < lens[s:s + k, None]]
-    del rows
+    if wl == "longp":
+        data, offsets = long_rows_batch(words, dev)
+        n = offsets.numel() - 1
+        chars = int(offsets[-1].item())
+    else:
+        lens = (torch.arange(n, device=dev, dtype=torch.int64) * 2654435761 % 256 + 1)
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(lens, 0)
+        col = torch.arange(256, device=dev)[None, :]
+        chars = int(offsets[-1].item())
+        rows = bench.make_rows(base, words, 0, n, dev)
+        data = torch.empty(chars, dtype=torch.uint8, device=dev)
+        for s in range(0, n, 1 << 20):
+            k = min(1 << 20, n - s)
+            data[int(offsets[s].item()):int(offsets[s + k].item())] = rows[s:s + k][col < lens[s:s + k, None]]
+        del rows
     pv = _lib.PackedView()
     pv.data, pv.char_width, pv.n_rows, pv.offsets = data.data_ptr(), 1, n, offsets.data_ptr()
     h = pattern._h
@@ -100,31 +145,36 @@ def lane_child(args, wl):
     sums = (m, int(st.to(torch.int64).sum().item()), int(en.to(torch.int64).sum().item()))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ms = []
+    launches = 0
     for r in range(args.warmup + args.steps):
+        if r == args.warmup:
+            launches = pattern.prefilter_state("forwards")["filter_launches"]
         e0.record()
         step()
         e1.record()
         e1.synchronize()
         if r >= args.warmup:
             ms.append(e0.elapsed_time(e1))
+    launches = pattern.prefilter_state("forwards")["filter_launches"] - launches
     actual = chars + n * 8 + (n * 8 + 8) + n * 4 + m * 8
     med = sorted(ms)[len(ms) // 2]
     print(json.dumps({"workload": wl, "what": what, "route": route, "rows": n, "chars": chars, "matches": sums[0], "checksum_start": sums[1],
                       "checksum_end": sums[2], "ms": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
-                      "GB/s": round(actual / med / 1e6, 1), "actual_bytes": actual}), flush=True)
+                      "GB/s": round(actual / med / 1e6, 1), "actual_bytes": actual, "filter_launches_per_step": round(launches / max(len(ms), 1), 2)}), flush=True)
 
 
 def lane_parent(args, wl):
-    """(a) lane, (b) conversion, (a), (b): one child at a time.  This process never opens the GPU."""
+    """(a) the lane / filter route, (b) conversion, (a), (b): one child at a time.  This process never opens the GPU."""
     import subprocess
     runs = []
+    switch, name = SWITCH[wl]
     for tag, env_val in (("a", "1"), ("b", "0"), ("a", "1"), ("b", "0")):
-        env = dict(os.environ, NEEDLE_PACKED_FIND_ALL_LANE=env_val)
+        env = dict(os.environ, **{switch: env_val})
         cmd = [sys.executable, os.path.abspath(__file__), "--lane-child", wl, "--rows", str(args.rows), "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--nested-min-len", str(args.nested_min_len)]
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, timeout=args.child_timeout, check=True)
         out = json.loads(r.stdout.decode().strip().split("\n")[-1])
-        assert out["route"] == ("lane" if tag == "a" else "conversion"), out
+        assert out["route"] == (name if tag == "a" else "conversion"), out
         out["tag"] = tag
         runs.append(out)
         print(json.dumps(out), flush=True)
@@ -132,8 +182,8 @@ def lane_parent(args, wl):
     assert len(same) == 1, same  # every route and run: the same matches
     a = [r["ms"] for r in runs if r["tag"] == "a"]
     b = [r["ms"] for r in runs if r["tag"] == "b"]
-    print(json.dumps({"workload": wl, "summary": True, "matches": runs[0]["matches"], "lane_ms": a, "conversion_ms": b,
-                      "lane_over_conversion": round((sum(a) / len(a)) / (sum(b) / len(b)), 3)}), flush=True)
+    print(json.dumps({"workload": wl, "summary": True, "matches": runs[0]["matches"], name + "_ms": a, "conversion_ms": b,
+                      name + "_over_conversion": round((sum(a) / len(a)) / (sum(b) / len(b)), 3)}), flush=True)
 
 
 def main():
@@ -151,9 +201,9 @@ def main():
         return lane_child(args, args.lane_child)
     wanted = args.only.split(",")
     for wl in wanted:
-        if wl in LANE_WORKLOADS:
+        if wl in SWITCH:
             lane_parent(args, wl)
-    args.only = ",".join(w for w in wanted if w not in LANE_WORKLOADS)
+    args.only = ",".join(w for w in wanted if w not in SWITCH)
     if not args.only:
         return
     import torch

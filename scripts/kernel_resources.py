@@ -17,7 +17,8 @@ for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", 
            "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2", "needle_packed_next1",
            "needle_packed_next2", "needle_packed_forms1", "needle_packed_forms2",
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
-           "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2"):
+           "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2",
+           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
                                          "-S", "-o", out, os.path.join(CSRC, tu + ".hip")], stderr=subprocess.DEVNULL)))
