@@ -340,6 +340,11 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         return new Matches(matchOffsets, start, end);
     }
 
+    /** The native pattern (GpuPatternSet copies its tables at creation). */
+    long handle() {
+        return handle;
+    }
+
     @Override
     public void close() {
         if (handle != 0) {

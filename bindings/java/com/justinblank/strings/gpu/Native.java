@@ -66,6 +66,17 @@ final class Native {
 
     static native int findPacked8Host(long handle, char[] data, long[] offsets, long[] bitmap, short[] startLen);
 
+    /**
+     * Pattern sets (needle_pattern_set_*): 1 .. 32 patterns answered in one pass over a packed batch.  setCreate copies the patterns'
+     * tables (the patterns may be closed afterwards); setPackedHost: op 0 matches, 1 containedIn; data + offsets as packedHost;
+     * masks int[n]: bit i of masks[r] = what pattern i answers for haystack r.
+     */
+    static native int setCreate(long[] patterns, long[] handleOut);
+
+    static native void setDestroy(long set);
+
+    static native int setPackedHost(long set, int op, char[] data, long[] offsets, int[] masks);
+
     /** needle_find_all_host: counts int[nRows]; start / end int[nRows * maxPerRow]; more int[1]. */
     static native int findAllHost(long handle, java.nio.ByteBuffer rows, int charWidth, long nRows, long rowStride, int rowLen,
                                   java.nio.ByteBuffer lengths, int maxPerRow, int[] counts, int[] start, int[] end, int[] more);

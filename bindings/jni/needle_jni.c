@@ -391,6 +391,46 @@ NATIVE(jint, findPacked8Host)(JNIEnv *env, jclass c, jlong h, jcharArray data, j
     return find_packed_compact_host(env, h, data, offsets, bitmap, startLen, 8);
 }
 
+/* Pattern sets: needle_pattern_set_create / _destroy and the two packed host entries (op 0 matches, 1 containedIn); masks int[n]. */
+NATIVE(jint, setCreate)(JNIEnv *env, jclass c, jlongArray patterns, jlongArray out) {
+    if (!patterns || !out || (*env)->GetArrayLength(env, out) < 1) return NEEDLE_ERR_INVALID;
+    const jsize n = (*env)->GetArrayLength(env, patterns);
+    if (n < 1 || n > NEEDLE_SET_MAX_PATTERNS) return NEEDLE_ERR_INVALID;
+    jlong *h = (*env)->GetLongArrayElements(env, patterns, NULL);
+    if (!h) return NEEDLE_ERR_INVALID;
+    const needle_pattern *ps[NEEDLE_SET_MAX_PATTERNS];
+    for (jsize i = 0; i < n; ++i) ps[i] = (const needle_pattern *)(intptr_t)h[i];
+    needle_pattern_set *s = NULL;
+    int rc = needle_pattern_set_create(ps, (int)n, &s);
+    (*env)->ReleaseLongArrayElements(env, patterns, h, JNI_ABORT);
+    jlong sh = (jlong)(intptr_t)s;
+    (*env)->SetLongArrayRegion(env, out, 0, 1, &sh);
+    return rc;
+}
+
+NATIVE(void, setDestroy)(JNIEnv *env, jclass c, jlong s) { needle_pattern_set_destroy((needle_pattern_set *)(intptr_t)s); }
+
+NATIVE(jint, setPackedHost)(JNIEnv *env, jclass c, jlong s, jint op, jcharArray data, jlongArray offsets, jintArray masks) {
+    if (!data || !offsets || !masks || (op != 0 && op != 1)) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, masks) < n1 - 1) return NEEDLE_ERR_INVALID;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jint *m = (*env)->GetIntArrayElements(env, masks, NULL);
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    const needle_pattern_set *ps = (const needle_pattern_set *)(intptr_t)s;
+    int rc = op == 0 ? needle_set_matches_packed_host(ps, &v, (uint32_t *)m) : needle_set_contained_in_packed_host(ps, &v, (uint32_t *)m);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, masks, m, 0);
+    return rc;
+}
+
 NATIVE(jbyteArray, serialize)(JNIEnv *env, jclass c, jlong h) {
     size_t need = 0;
     const needle_pattern *p = (const needle_pattern *)(intptr_t)h;

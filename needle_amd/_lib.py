@@ -19,6 +19,8 @@ EXPORTS = [
     "needle_contained_in_packed_host", "needle_find_packed_host", "needle_count_matches_packed_dev", "needle_find_all_csr_packed_dev",
     "needle_find_all_compact16_packed_dev", "needle_find_all_csr_packed_host", "needle_find_next_packed_dev", "needle_find_packed16_packed_dev",
     "needle_find_packed8_packed_dev", "needle_find_packed16_packed_host", "needle_find_packed8_packed_host",
+    "needle_pattern_set_create", "needle_pattern_set_destroy", "needle_pattern_set_info", "needle_pattern_set_get_tables",
+    "needle_set_matches_packed_dev", "needle_set_contained_in_packed_dev", "needle_set_matches_packed_host", "needle_set_contained_in_packed_host",
     "needle_multi_create", "needle_multi_destroy", "needle_multi_device_count", "needle_multi_stream", "needle_multi_transport", "needle_multi_scan",
     "needle_multi_sync", "needle_scan_host_multi", "needle_multi_unique_id", "needle_multi_create_rank",
     "needle_multi_all_gather_u64", "needle_multi_gather_i32",
@@ -69,6 +71,11 @@ class PrefilterInfo(ctypes.Structure):
 
 class PrefilterInfo2(ctypes.Structure):
     _fields_ = [("base", PrefilterInfo), ("wide", ctypes.c_int32), ("m1b", ctypes.c_uint32), ("m2b", ctypes.c_uint32)]
+
+
+class SetInfo(ctypes.Structure):
+    _fields_ = ([("n_patterns", ctypes.c_int32), ("n_groups", ctypes.c_int32)] +
+                [(k, ctypes.c_int32 * 32) for k in ("first_pattern", "pattern_count", "n_states", "n_columns", "kernel_mode", "lds_bytes")])
 
 
 _lib = None
@@ -153,6 +160,15 @@ def lib():
     L.needle_find_packed8_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP]
     L.needle_find_packed16_packed_host.argtypes = [VP, P(PackedView), VP, VP]
     L.needle_find_packed8_packed_host.argtypes = [VP, P(PackedView), VP, VP]
+    L.needle_pattern_set_create.argtypes = [P(VP), I, P(VP)]
+    L.needle_pattern_set_destroy.argtypes = [VP]
+    L.needle_pattern_set_destroy.restype = None
+    L.needle_pattern_set_info.argtypes = [VP, I, I, P(SetInfo)]
+    L.needle_pattern_set_get_tables.argtypes = [VP, I, I, I, VP, P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_int32), VP, ctypes.c_size_t, VP, ctypes.c_size_t]
+    for n in ("needle_set_matches_packed_dev", "needle_set_contained_in_packed_dev"):
+        getattr(L, n).argtypes = [VP, P(PackedView), VP, VP]
+    for n in ("needle_set_matches_packed_host", "needle_set_contained_in_packed_host"):
+        getattr(L, n).argtypes = [VP, P(PackedView), VP]
     L.needle_matcher_create.argtypes = [VP, VP, ctypes.c_size_t, P(VP)]
     L.needle_matcher_destroy.argtypes = [VP]
     L.needle_matcher_destroy.restype = None

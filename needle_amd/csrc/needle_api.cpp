@@ -19,6 +19,7 @@
 #include "needle_launch.h"
 #include "needle_lower.h"
 #include "needle_regex.h"
+#include "needle_set.h"
 
 using namespace needle;
 
@@ -3002,5 +3003,219 @@ int needle_matcher_find(needle_matcher *m, int *r) {
 
 int needle_matcher_start(const needle_matcher *m) { return m ? m->start : -1; }
 int needle_matcher_end(const needle_matcher *m) { return m ? m->end : -1; }
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Pattern sets: up to 32 patterns in one pass over a packed batch (needle_set.h: the products and their groups; needle_packed_set.h: the kernel)
+// ------------------------------------------------------------------------------------------------
+struct needle_pattern_set {
+    std::vector<RefTables> members; // copies: the patterns may be destroyed
+    SetPlan plan[2][2];             // [op][char_width - 1], built at creation (host only)
+    std::string refused[2][2];      // non-empty: why this plan could not be built (UTF-16 plans only: a refused 8-bit plan fails the creation)
+    std::mutex mu;
+    std::map<std::tuple<int, int, int, int>, uint8_t *> resident; // (device, op, char_width, group) -> the group's program in that device's HBM
+    std::map<int, int> cus;                                       // device -> CU count
+    ~needle_pattern_set() {
+        for (auto &kv : resident)
+            if (kv.second) (void)hipFree(kv.second);
+    }
+};
+
+static const SetPlan *set_plan(const needle_pattern_set *s, int op, int char_width) {
+    if (!s || (op != OP_MATCHES && op != OP_CONTAINED_IN) || (char_width != 1 && char_width != 2)) return nullptr;
+    return &s->plan[op][char_width - 1];
+}
+// NEEDLE_ERR_UNSUPPORTED where the set has no plan for this op and char width (arguments as set_plan accepts them).
+static int set_plan_usable(const needle_pattern_set *s, int op, int char_width) {
+    const std::string &why = s->refused[op][char_width - 1];
+    return why.empty() ? NEEDLE_OK : fail(NEEDLE_ERR_UNSUPPORTED, why);
+}
+
+// One group's program on the current device, built on first use and cached in the set (as get_program does for patterns).
+static int set_program(needle_pattern_set *s, int op, int cw, int group, const uint8_t **d_blob, int *n_cus) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->cus.count(dev)) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        s->cus[dev] = prop.multiProcessorCount;
+    }
+    *n_cus = s->cus[dev];
+    const auto key = std::make_tuple(dev, op, cw, group);
+    auto it = s->resident.find(key);
+    if (it == s->resident.end()) {
+        const Program &pr = s->plan[op][cw - 1].groups[(size_t)group].prog;
+        uint8_t *d = nullptr;
+        HIP_TRY(hipMalloc((void **)&d, pr.blob.size()));
+        if (hipError_t ce = hipMemcpy(d, pr.blob.data(), pr.blob.size(), hipMemcpyHostToDevice); ce != hipSuccess) {
+            (void)hipFree(d);
+            return hip_fail(ce, "hipMemcpy(pattern set program)");
+        }
+        it = s->resident.emplace(key, d).first;
+    }
+    *d_blob = it->second;
+    return NEEDLE_OK;
+}
+
+static int check_set_packed(const needle_pattern_set *s, const needle_packed_view *v, const uint32_t *masks, bool device) {
+    if (!s) return fail(NEEDLE_ERR_INVALID, "pattern set is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!masks) return fail(NEEDLE_ERR_INVALID, "masks is NULL");
+    if (device && ((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    return NEEDLE_OK;
+}
+
+// One launch per group on the caller's stream: group 0 stores the masks, later groups read-modify-write them.
+static int run_set_packed_dev(const needle_pattern_set *cs, int op, const needle_packed_view *v, uint32_t *d_masks, void *stream_) {
+    needle_pattern_set *s = const_cast<needle_pattern_set *>(cs);
+    int rc = check_set_packed(s, v, d_masks, true);
+    if (rc) return rc;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    const int cw = (int)v->char_width;
+    if ((rc = set_plan_usable(s, op, cw))) return rc;
+    const SetPlan &plan = s->plan[op][cw - 1];
+    for (size_t g = 0; g < plan.groups.size(); ++g) {
+        const SetGroup &grp = plan.groups[g];
+        const uint8_t *d_blob = nullptr;
+        int n_cus = 0;
+        if ((rc = set_program(s, op, cw, (int)g, &d_blob, &n_cus))) return rc;
+        PackedSetArgs a;
+        memset(&a, 0, sizeof(a));
+        a.p.s.rows = (const uint8_t *)v->data;
+        a.p.s.n_rows = v->n_rows;
+        a.p.s.prog = d_blob;
+        a.p.s.hdr = grp.prog.hdr;
+        a.p.s.fixed_len = -1;
+        a.p.offsets = v->offsets;
+        a.masks = d_masks;
+        a.group_mask = (grp.count >= 32 ? 0xFFFFFFFFu : ((1u << grp.count) - 1u)) << grp.first;
+        a.store = g == 0 ? 1u : 0u;
+        HIP_TRY(launch_packed_set(op, cw, a, n_cus, (hipStream_t)stream_));
+    }
+    return NEEDLE_OK;
+}
+
+// A packed HOST batch: consecutive-row chunks of at most NEEDLE_HOST_CHUNK_BYTES of text are uploaded (offsets rebased to the chunk),
+// scanned where they lie by the _dev entry and their masks downloaded -- the chunking and upload of needle_find_packed16_packed_host.
+static int run_set_packed_host(const needle_pattern_set *s, int op, const needle_packed_view *v, uint32_t *masks) {
+    int rc = check_set_packed(s, v, masks, false);
+    if (rc) return rc;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if ((rc = set_plan_usable(s, op, (int)v->char_width))) return rc;
+    const uint64_t n = v->n_rows, cw = v->char_width;
+    uint64_t max_len = 0;
+    if ((rc = check_packed_host_offsets(v, &max_len))) return rc;
+    if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
+    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+    const std::vector<std::pair<uint64_t, uint64_t>> chunks = packed_host_chunks(v, 8 + 4, 1); // (offset + mask per row)
+    uint64_t biggest = 0, max_rows = 0;
+    for (const auto &c : chunks) {
+        biggest = std::max<uint64_t>(biggest, up16(std::max<uint64_t>((v->offsets[c.second] - v->offsets[c.first]) * cw, 4)));
+        max_rows = std::max<uint64_t>(max_rows, c.second - c.first);
+    }
+    // data | offsets | masks (one buffer for every chunk)
+    const uint64_t o_off = biggest, o_res = o_off + up16((max_rows + 1) * 8), all = o_res + up16(max_rows * 4);
+    DevAllocs dev;
+    uint8_t *d = nullptr;
+    HIP_TRY(dev.alloc(&d, all));
+    std::vector<uint64_t> local;
+    for (const auto &c : chunks) {
+        const uint64_t r0 = c.first, nr = c.second - c.first;
+        needle_packed_view dv;
+        hipError_t e = upload_packed_chunk(v, r0, c.second, d, (uint64_t *)(d + o_off), local, &dv);
+        if (e != hipSuccess) return hip_fail(e, "set_packed_host upload");
+        if ((rc = run_set_packed_dev(s, op, &dv, (uint32_t *)(d + o_res), nullptr))) return rc;
+        e = hipMemcpy(masks + r0, d + o_res, nr * 4, hipMemcpyDeviceToHost); // (synchronises with the scan)
+        if (e != hipSuccess) return hip_fail(e, "set_packed_host download");
+    }
+    return NEEDLE_OK;
+}
+
+extern "C" {
+
+int needle_pattern_set_create(const needle_pattern *const *patterns, int n_patterns, needle_pattern_set **out) {
+    if (!out) return fail(NEEDLE_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!patterns) return fail(NEEDLE_ERR_INVALID, "patterns is NULL");
+    if (n_patterns < 1 || n_patterns > NEEDLE_SET_MAX_PATTERNS) return fail(NEEDLE_ERR_INVALID, "a pattern set holds 1 .. 32 patterns");
+    std::unique_ptr<needle_pattern_set> s(new needle_pattern_set);
+    for (int i = 0; i < n_patterns; ++i) {
+        if (!patterns[i]) return fail(NEEDLE_ERR_INVALID, "pattern " + std::to_string(i) + " of the set is NULL");
+        s->members.push_back(patterns[i]->t);
+    }
+    for (int op = 0; op < 2; ++op)
+        for (int cw = 1; cw <= 2; ++cw) {
+            int bad = -1;
+            if (build_set_plan(s->members, op, cw, max_prog_lds(), &s->plan[op][cw - 1], &bad)) continue;
+            const std::string why = "pattern " + std::to_string(bad) + " of the set does not fit the LDS as a plain table (" +
+                                    (op == OP_MATCHES ? "matches" : "containedIn") + ", char_width " + std::to_string(cw) +
+                                    "): run it alone, behind the n-gram filter";
+            // The UTF-16 column maps hold less than the 8-bit one (columns x element size <= 255): a member they refuse alone must not
+            // keep a caller of 8-bit rows from the set -- that plan is refused where it is asked for (info, tables, scans of UTF-16 rows).
+            if (cw == 1) return fail(NEEDLE_ERR_UNSUPPORTED, why);
+            s->refused[op][cw - 1] = why;
+        }
+    *out = s.release();
+    return NEEDLE_OK;
+}
+
+void needle_pattern_set_destroy(needle_pattern_set *s) { delete s; }
+
+int needle_pattern_set_info(const needle_pattern_set *s, int op, int char_width, needle_set_info *o) {
+    const SetPlan *plan = set_plan(s, op, char_width);
+    if (!plan || !o) return fail(NEEDLE_ERR_INVALID, "pattern_set_info: bad argument");
+    if (int rc = set_plan_usable(s, op, char_width)) return rc;
+    memset(o, 0, sizeof(*o));
+    o->n_patterns = (int32_t)s->members.size();
+    o->n_groups = (int32_t)plan->groups.size();
+    for (size_t g = 0; g < plan->groups.size(); ++g) {
+        const SetGroup &grp = plan->groups[g];
+        o->first_pattern[g] = grp.first;
+        o->pattern_count[g] = grp.count;
+        o->n_states[g] = grp.prod.n_states;
+        o->n_columns[g] = grp.prod.n_classes + 2;
+        o->kernel_mode[g] = (int32_t)grp.prog.hdr.mode;
+        o->lds_bytes[g] = (int32_t)grp.prog.hdr.lds_bytes;
+    }
+    return NEEDLE_OK;
+}
+
+int needle_pattern_set_get_tables(const needle_pattern_set *s, int op, int char_width, int group, uint8_t *class_map, int32_t *n_classes,
+                                  int32_t *n_states, int32_t *start, int32_t *table, size_t table_cap, uint32_t *masks, size_t masks_cap) {
+    const SetPlan *plan = set_plan(s, op, char_width);
+    if (!plan) return fail(NEEDLE_ERR_INVALID, "pattern_set_get_tables: bad argument");
+    if (int rc = set_plan_usable(s, op, char_width)) return rc;
+    if (group < 0 || (size_t)group >= plan->groups.size()) return fail(NEEDLE_ERR_INVALID, "pattern_set_get_tables: bad argument");
+    const SetProduct &sp = plan->groups[(size_t)group].prod;
+    if (n_classes) *n_classes = sp.n_classes;
+    if (n_states) *n_states = sp.n_states;
+    if (start) *start = sp.start;
+    if (class_map) memcpy(class_map, sp.class_map.data(), 65536);
+    if (table) {
+        if (table_cap < sp.table.size()) return fail(NEEDLE_ERR_INVALID, "pattern_set_get_tables: table buffer too small");
+        memcpy(table, sp.table.data(), sp.table.size() * 4);
+    }
+    if (masks) {
+        if (masks_cap < sp.mask.size()) return fail(NEEDLE_ERR_INVALID, "pattern_set_get_tables: masks buffer too small");
+        memcpy(masks, sp.mask.data(), sp.mask.size() * 4);
+    }
+    return NEEDLE_OK;
+}
+
+int needle_set_matches_packed_dev(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *d_masks, void *stream) {
+    return run_set_packed_dev(s, OP_MATCHES, v, d_masks, stream);
+}
+int needle_set_contained_in_packed_dev(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *d_masks, void *stream) {
+    return run_set_packed_dev(s, OP_CONTAINED_IN, v, d_masks, stream);
+}
+int needle_set_matches_packed_host(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *masks) {
+    return run_set_packed_host(s, OP_MATCHES, v, masks);
+}
+int needle_set_contained_in_packed_host(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *masks) {
+    return run_set_packed_host(s, OP_CONTAINED_IN, v, masks);
+}
 
 } // extern "C"

@@ -111,6 +111,7 @@ struct ProgHeader {
     // codes, numbered 1, 3, .. 15 (bit 0 of an entry = "a match ends here").
     // ft_direct: every code has k = 0 and names its own length -- no table lookup when a match is filed: 1 = the code is the length (1 .. 15),
     // 2 = the code is length << 1 | 1 (lengths 1 .. 7; ft_odd holds too).
+    // (pattern-set programs, needle_lower.h lower_pattern_set: ft_on = 0 and ft_codes_off = LDS offset of uint32 mask[device state])
     uint32_t ft_on, ft_codes_off, ft_odd, ft_direct;
     uint32_t off_bpack;  // != 0: the backward automaton has <= 5 states and rides along as packed functions: 8-bit rows
                          // u32 F[256] there; UTF-16 rows ptab64[256] there ({absolute F address, mask} per high byte)
@@ -154,6 +155,14 @@ struct PackedArgs {
                               // dword / uint16 per row with escapes, pack16_or_over / pack8_or_over below).
     const uint64_t *offsets;  // n_rows + 1 entries (device)
     int32_t *overflow;        // optional, with s.packed: set to 1 when some row's match escaped its form
+};
+
+// The pattern-set kernel of packed rows (needle_packed_set.h): one launch per group of the set (needle_set.h).
+struct PackedSetArgs {
+    PackedArgs p;         // FIRST member (as PackedArgs::s).  Used: s.rows, s.n_rows, s.prog / s.hdr (a lower_pattern_set program), offsets
+    uint32_t *masks;      // n_rows result words (device)
+    uint32_t group_mask;  // the group's bits: a containedIn() row that holds them all is decided
+    uint32_t store;       // != 0: masks[r] = the group's bits (the set's first group); 0: masks[r] |= them (stream-ordered, one lane per row)
 };
 
 // Long rows of table-mode automata (needle_stripe.hip, "speculative stripes"): every stripe is first scanned as a row of

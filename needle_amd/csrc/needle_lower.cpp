@@ -1297,6 +1297,89 @@ Program lower_match_lengths(const RefTables &t, const MatchLengths &ml, int char
     return lower(t, W_FORWARDS, char_width, lds_table_budget, false, false, plain, &ml);
 }
 
+// ---- pattern sets (needle_lower.h) -----------------------------------------------------------------------------------------------
+// The product's char -> column maps: its combined class map in the layout column_maps() gives one automaton's.
+static ColumnMaps set_column_maps(const SetProduct &sp, int char_width) {
+    RefTables t;
+    t.class_map = sp.class_map;
+    t.stride = sp.n_classes;
+    RefDfa d; // (max_char 0xFFFF: no OVER column)
+    return column_maps(t, d, char_width);
+}
+static uint32_t set_elem(int n_states) { return n_states + 1 <= 256 ? 1u : 2u; }
+
+size_t pattern_set_front_bytes(const SetProduct &sp, int char_width) {
+    if (char_width == 1) return 512;
+    return ((kLdsPages2Table + set_column_maps(sp, 2).pages.size()) + 15) & ~(size_t)15;
+}
+
+size_t pattern_set_program_bytes(const SetProduct &sp, size_t front, int n_states, int char_width) {
+    const size_t n_dev = (size_t)n_states + 1, n_cols = (size_t)sp.n_classes + 2, elem = set_elem(n_states);
+    if (n_dev > 65535 || sp.n_classes > 254 || (char_width == 2 && n_cols * elem > 255)) return 0;
+    return front + ((n_dev * n_cols * elem + 15) & ~(size_t)15) + ((n_dev * 4 + 15) & ~(size_t)15);
+}
+
+Program lower_pattern_set(const SetProduct &sp, int char_width, size_t lds_table_budget) {
+    Program p;
+    memset(&p.hdr, 0, sizeof(p.hdr));
+    const size_t want = pattern_set_program_bytes(sp, pattern_set_front_bytes(sp, char_width), sp.n_states, char_width);
+    if (want == 0 || want > lds_table_budget || want > kMaxProgLdsBytes) return p;
+    const int n_ref = sp.n_states, n_dev = n_ref + 1, N = sp.n_classes, n_cols = N + 2, PAD = N, PRE = N + 1;
+    // device numbering: 0 sink | states without bits | states with bits
+    std::vector<int> dev(n_ref);
+    int next_id = 1;
+    for (int s = 0; s < n_ref; ++s)
+        if (!sp.mask[s]) dev[s] = next_id++;
+    const int accept_lo = next_id;
+    for (int s = 0; s < n_ref; ++s)
+        if (sp.mask[s]) dev[s] = next_id++;
+    std::vector<uint16_t> next((size_t)n_dev * n_cols, 0); // sink row: all 0
+    std::vector<uint32_t> mask(n_dev, 0);
+    for (int s = 0; s < n_ref; ++s) {
+        uint16_t *row = &next[(size_t)dev[s] * n_cols];
+        for (int k = 0; k < N; ++k) {
+            const int32_t tgt = sp.table[(size_t)s * N + k];
+            row[k] = (uint16_t)(tgt < 0 ? 0 : dev[tgt]);
+        }
+        row[PAD] = row[PRE] = (uint16_t)dev[s];
+        mask[dev[s]] = sp.mask[s];
+    }
+    const uint32_t elem = set_elem(n_ref);
+    const ColumnMaps cm = set_column_maps(sp, char_width);
+    auto put16 = [&](size_t off, uint32_t v) { p.blob[off] = (uint8_t)(v & 255); p.blob[off + 1] = (uint8_t)(v >> 8); };
+    if (char_width == 1) {
+        p.blob.assign(512, 0); // cmap16 at kLdsCmap1 = 0
+        for (int c = 0; c < 256; ++c) put16(kLdsCmap1 + 2 * c, cm.cmap8[c] * elem);
+    } else {
+        p.blob.assign(kLdsPages2Table + cm.pages.size(), 0);
+        for (int hi = 0; hi < 256; ++hi) put16(kLdsPtab2 + 2 * hi, (uint32_t)cm.ptab[hi] * 256u);
+        for (size_t i = 0; i < cm.pages.size(); ++i) p.blob[kLdsPages2Table + i] = (uint8_t)(cm.pages[i] * elem);
+    }
+    if (elem == 1) {
+        std::vector<uint8_t> t8(next.size());
+        for (size_t i = 0; i < next.size(); ++i) t8[i] = (uint8_t)next[i];
+        p.hdr.off_table = append(p.blob, t8.data(), t8.size());
+    } else {
+        p.hdr.off_table = append(p.blob, next.data(), next.size() * 2);
+    }
+    p.hdr.ft_codes_off = append(p.blob, mask.data(), mask.size() * 4);
+    while (p.blob.size() % 16) p.blob.push_back(0);
+    if (p.blob.size() != want || (char_width == 1 && p.hdr.off_table != kLdsTable1)) { // (the estimate and the image must agree)
+        p.blob.clear();
+        return p;
+    }
+    p.hdr.mode = elem == 1 ? MODE_TABLE8 : MODE_TABLE16;
+    p.hdr.n_states = (uint32_t)n_dev;
+    p.hdr.n_cols = (uint32_t)n_cols;
+    p.hdr.start = (uint32_t)dev[sp.start];
+    p.hdr.accept_lo = (uint32_t)accept_lo;
+    p.hdr.root_accepting = sp.mask[sp.start] ? 1u : 0u;
+    p.hdr.pad_col = (uint32_t)PAD;
+    p.hdr.n_pages = (uint32_t)(cm.pages.size() / 256);
+    p.hdr.lds_bytes = (uint32_t)p.blob.size();
+    return p;
+}
+
 
 // ---- the find-all transducer (needle_lower.h) -------------------------------------------------------------------------------------
 // The device image of a find-all transducer (both kinds below): tab[state][NC] = target << 4 | code in reference columns (classes, OVER,

@@ -101,4 +101,28 @@ Program lower_find_all_transducer(const RefTables &t, const MatchLengths &ml, in
 // (needle_find_all_ls.hip).  hdr.ft_on = 2.  empty blob: not such a pattern.
 Program lower_find_all_runs(const RefTables &t, int char_width, size_t lds_table_budget);
 
+// ---- pattern sets (needle_set.h): up to 32 patterns answered by ONE automaton ------------------------------------------------
+// A product automaton over a combined class map, as needle_set.cpp builds it from the members' reference tables: ref state 0.. in
+// breadth-first order, `start` its start state, table[state * n_classes + class] = the next state (-1: every component is dead --
+// matches() products only), mask[state] = bit i set when member i of the group stands in an accepting state.
+struct SetProduct {
+    int n_classes = 0;
+    std::vector<uint8_t> class_map; // 65536: char -> combined class (the members' max_char rules are folded in: no OVER column);
+                                    // a product for 8-bit rows tells only the chars below 256 apart (the entries above them are 0)
+    int n_states = 0, start = 0;
+    std::vector<int32_t> table;
+    std::vector<uint32_t> mask;
+};
+// Bytes of the column maps in front of a product's table (they depend on its class map alone: computed once per product).
+size_t pattern_set_front_bytes(const SetProduct &sp, int char_width);
+// Bytes of the device program of a product with n_states ref states behind `front` bytes of column maps (what lower_pattern_set would
+// emit): the test the product's breadth-first construction aborts on.  0: the columns do not fit the column maps of this char width.
+size_t pattern_set_program_bytes(const SetProduct &sp, size_t front, int n_states, int char_width);
+// The device program of a product, modelled on lower_match_lengths: plain table modes only (MODE_TABLE8 / MODE_TABLE16, no window
+// addressing, no pair table), columns = the combined classes, PAD, PRE (both identities), device state 0 = the sink, the states with
+// a non-zero mask numbered from hdr.accept_lo up ("st >= accept_lo" = "this state has bits"), uint32 mask[device state] in the LDS
+// part at hdr.ft_codes_off (a field that means nothing for a program that is no find-all transducer).  Empty blob: it does not fit
+// lds_table_budget (or the column maps).
+Program lower_pattern_set(const SetProduct &sp, int char_width, size_t lds_table_budget);
+
 } // namespace needle

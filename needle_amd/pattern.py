@@ -1042,6 +1042,105 @@ class Pattern:
         return rows, lengths, overflow
 
 
+SET_OPS = {"matches": 0, "contained_in": 1}
+
+
+class PatternSet:
+    """1 .. 32 compiled patterns answered in ONE pass over a packed batch (needle_pattern_set, include/needle_hip.h): bit i of a row's
+    mask is what matches() / containedIn() of patterns[i] returns for that row.  The patterns' tables are copied: the Pattern objects
+    may go away.  A pattern whose automaton does not fit the LDS as a plain table (a big dictionary) is refused
+    (PatternClassCompilationException naming its index)."""
+
+    def __init__(self, patterns):
+        patterns = list(patterns)
+        arr = (ctypes.c_void_p * max(1, len(patterns)))(*[getattr(p, "_h", None) for p in patterns])
+        h = ctypes.c_void_p()
+        _check(_lib.lib().needle_pattern_set_create(arr, len(patterns), ctypes.byref(h)))
+        self._h = h
+        self.n_patterns = len(patterns)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None and _lib._lib is not None:
+            _lib._lib.needle_pattern_set_destroy(h)
+
+    def info(self, op="contained_in", char_width=1):
+        """The groups of one op and char width (host-side: needs no GPU): {"n_patterns", "n_groups", "groups": [{"first_pattern",
+        "pattern_count", "n_states", "n_columns", "kernel_mode", "lds_bytes"}, ...]}."""
+        i = _lib.SetInfo()
+        _check(_lib.lib().needle_pattern_set_info(self._h, SET_OPS[op], int(char_width), ctypes.byref(i)))
+        keys = ("first_pattern", "pattern_count", "n_states", "n_columns", "kernel_mode", "lds_bytes")
+        return {"n_patterns": i.n_patterns, "n_groups": i.n_groups,
+                "groups": [{k: getattr(i, k)[g] for k in keys} for g in range(i.n_groups)]}
+
+    def tables(self, op="contained_in", char_width=1, group=0):
+        """One group's product automaton on the host: {"class_map" uint8[65536], "n_classes", "n_states", "start", "table" int32[n_states,
+        n_classes] (-1: every component dead), "masks" uint32[n_states]}."""
+        L = _lib.lib()
+        nc, ns, st = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        args = (self._h, SET_OPS[op], int(char_width), int(group))
+        _check(L.needle_pattern_set_get_tables(*args, None, ctypes.byref(nc), ctypes.byref(ns), ctypes.byref(st), None, 0, None, 0))
+        cm = np.zeros(65536, dtype=np.uint8)
+        table = np.zeros(ns.value * nc.value, dtype=np.int32)
+        masks = np.zeros(ns.value, dtype=np.uint32)
+        _check(L.needle_pattern_set_get_tables(*args, cm.ctypes.data, None, None, None, table.ctypes.data, table.size, masks.ctypes.data, masks.size))
+        return {"class_map": cm, "n_classes": nc.value, "n_states": ns.value, "start": st.value,
+                "table": table.reshape(ns.value, nc.value), "masks": masks}
+
+    def _run_packed(self, op, data, offsets, stream, out):
+        L = _lib.lib()
+        if not isinstance(data, np.ndarray) and type(data).__module__.startswith("torch") and data.is_cuda:
+            import torch
+            assert data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), \
+                "data: 1-D uint8 or (u)int16 code units"
+            assert isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.device == data.device, "offsets: on data's device"
+            assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1, \
+                "offsets: 1-D int64, n + 1 entries"
+            n = offsets.numel() - 1
+            v = _lib.PackedView()
+            v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+            with torch.cuda.device(data.device):
+                s = torch.cuda.current_stream(data.device).cuda_stream if stream is None else stream
+                if out is not None:  # a caller-owned result buffer (at least n_rows int32)
+                    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
+                    masks = out
+                else:
+                    masks = torch.empty(n, dtype=torch.int32, device=data.device)
+                fn = L.needle_set_matches_packed_dev if op == "matches" else L.needle_set_contained_in_packed_dev
+                _check(fn(self._h, ctypes.byref(v), masks.data_ptr(), s))
+            return masks
+        data = np.ascontiguousarray(data)
+        if data.dtype == np.int16:
+            data = data.view(np.uint16)
+        assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+        masks = np.zeros(n, dtype=np.uint32)
+        fn = L.needle_set_matches_packed_host if op == "matches" else L.needle_set_contained_in_packed_host
+        _check(fn(self._h, ctypes.byref(v), masks.ctypes.data))
+        return masks
+
+    def matches_packed(self, data, offsets, stream=None, out=None):
+        """Masks of matches() of every packed row.  Device tensors (1-D uint8 | (u)int16 data, int64 offsets[n + 1]) ->
+        needle_set_matches_packed_dev, an int32 device tensor of n_rows masks (bit i: patterns[i]; stream-ordered); numpy data + offsets
+        -> needle_set_matches_packed_host, uint32[n_rows]."""
+        return self._run_packed("matches", data, offsets, stream, out)
+
+    def contained_in_packed(self, data, offsets, stream=None, out=None):
+        """Masks of containedIn() of every packed row (as matches_packed)."""
+        return self._run_packed("contained_in", data, offsets, stream, out)
+
+    def matches_strings(self, strings):
+        """matches() masks of a list of str (UTF-16 code units, like java.lang.String): pack_strings + the host entry -> uint32[n]."""
+        return self.matches_packed(*pack_strings(strings))
+
+    def contained_in_strings(self, strings):
+        """containedIn() masks of a list of str -> uint32[n]."""
+        return self.contained_in_packed(*pack_strings(strings))
+
+
 def pack_strings(strings):
     """list[str] -> (uint16 code units back to back, uint64 offsets[n + 1])."""
     units = [_utf16(x) for x in strings]
