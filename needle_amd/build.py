@@ -10,8 +10,7 @@ SOURCES = ["needle_scan_find1.hip", "needle_scan_find2.hip", "needle_scan_contai
            "needle_packed_find2.hip", "needle_packed_contained.hip", "needle_packed_matches.hip", "needle_packed_next1.hip", "needle_packed_next2.hip", "needle_packed_forms1.hip", "needle_packed_forms2.hip", "needle_packed_find_all1.hip",
            "needle_packed_find_all2.hip", "needle_packed_find_all_lane1.hip", "needle_packed_find_all_lane2.hip", "needle_packed_set1.hip", "needle_packed_set2.hip", "needle_kernels.hip",
            "needle_stripe.hip", "needle_find_all.hip", "needle_find_all_ls.hip", "needle_compact.hip", "needle_ngram.hip", "needle_ngram_packed_contained1.hip", "needle_ngram_packed_contained2.hip", "needle_ngram_packed_find1.hip",
-           "needle_ngram_packed_find2.hip", "needle_ngram_packed_find_all1.hip", "needle_ngram_packed_find_all2.hip", "needle_ngram_host.cpp", "needle_api.cpp", "needle_tuning.cpp", "needle_multi.cpp", "needle_lower.cpp", "needle_set.cpp", "needle_regex.cpp"]
-HEADERS = ["needle_device.h", "needle_launch.h", "needle_walk.h", "needle_scan.h", "needle_packed.h", "needle_packed_find_all.h", "needle_packed_find_all_lane.h", "needle_packed_set.h", "needle_set.h", "needle_find_all.h", "needle_find_all_walk.h", "needle_lower.h", "needle_regex.h", "needle_ngram.h", "needle_ngram_kernel.h", "needle_ngram_packed.h", "needle_ngram_host.h", "needle_unicode_tables.h", os.path.join("..", "..", "include", "needle_hip.h")]
+           "needle_ngram_packed_find2.hip", "needle_ngram_packed_find_all1.hip", "needle_ngram_packed_find_all2.hip", "needle_ngram_host.cpp", "needle_api.cpp", "needle_host.cpp", "needle_tuning.cpp", "needle_multi.cpp", "needle_lower.cpp", "needle_set.cpp", "needle_regex.cpp"]
 
 
 TUNING_LIB = os.path.join(HERE, "libneedle_hip_tuning.so")
@@ -35,7 +34,7 @@ def _stale(lib=LIB, sources=SOURCES):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in sources + HEADERS)
+    return any(os.path.getmtime(f) > t for src in sources for f in _deps(os.path.join(CSRC, src)))
 
 
 def _deps(path, seen=None):

@@ -1,5 +1,6 @@
-// C ABI of libneedle_hip.so (include/needle_hip.h): pattern objects, per-device program cache, batch entry
-// points, and the single-haystack Matcher mirror.  No CPU matching path exists in this library.
+// C ABI of libneedle_hip.so (include/needle_hip.h): pattern objects and pattern sets, the per-device program cache, the choice of the
+// scan route, and the batch entry points for rows in DEVICE memory.  The entries for rows in host memory and the Matcher mirror are
+// needle_host.cpp's, built on the _dev entries here.  No CPU matching path exists in this library.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <functional>
@@ -16,6 +17,7 @@
 #include "../../include/needle_hip.h"
 #include "needle_device.h"
 #include "needle_find_all.h"
+#include "needle_internal.h"
 #include "needle_launch.h"
 #include "needle_lower.h"
 #include "needle_regex.h"
@@ -38,7 +40,7 @@ static bool debug_no_backward() {
 #endif
 
 namespace needle {
-int set_error(int code, const std::string &msg) { return fail(code, msg); } // (needle_multi.cpp reports through the same channel)
+int set_error(int code, const std::string &msg) { return fail(code, msg); } // (the other translation units report through the same channel)
 } // namespace needle
 
 // Stream-ordered scratch memory comes from a pool of the library's own, one per device, that KEEPS what it is given back:
@@ -94,16 +96,6 @@ hipError_t scratch_malloc(void **out, size_t bytes, hipStream_t stream) {
 }
 hipError_t scratch_free(void *p, hipStream_t stream) { return hipFreeAsync(p, stream); }
 } // namespace needle
-
-static int hip_fail(hipError_t e, const char *what) {
-    return fail(NEEDLE_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
 
 struct DevProgram {
     Program prog;
@@ -196,6 +188,15 @@ struct needle_pattern {
         }
     }
 };
+
+needle::MatcherRoots needle::matcher_roots(const needle_pattern *p) {
+    auto root = [&](int w) { return !p->t.dfa[w].accepting.empty() && p->t.dfa[w].accepting[0] != 0; };
+    return {root(W_FORWARDS), root(W_BACKWARDS), p->t.fixed_len};
+}
+bool needle::find_all_rounds_forced() {
+    static const bool forced = (getenv("NEEDLE_FIND_ALL_ROUNDS") ? atoi(getenv("NEEDLE_FIND_ALL_ROUNDS")) : 0) != 0;
+    return forced;
+}
 
 // Automaton LDS budget.  NEEDLE_MAX_PROG_LDS (bytes) lowers it: tests use that to force the HBM-table mode.
 static size_t max_prog_lds() {
@@ -331,26 +332,15 @@ static int get_program(needle_pattern *p, int which, int cw, Variant variant, co
     return NEEDLE_OK;
 }
 
-static int check_view(const needle_batch_view *v, bool device) {
+static int check_view(const needle_batch_view *v) {
     if (!v) return fail(NEEDLE_ERR_INVALID, "batch view is NULL");
     if (v->char_width != 1 && v->char_width != 2) return fail(NEEDLE_ERR_INVALID, "char_width must be 1 or 2");
     if (v->n_rows && !v->rows) return fail(NEEDLE_ERR_INVALID, "rows is NULL");
     if (v->row_len > v->row_stride) return fail(NEEDLE_ERR_INVALID, "row_len > row_stride");
-    if (device) {
-        if ((v->row_stride * v->char_width) % 16 != 0)
-            return fail(NEEDLE_ERR_INVALID, "row_stride * char_width must be a multiple of 16 bytes for device batches");
-        if (((uintptr_t)v->rows) % 16 != 0) return fail(NEEDLE_ERR_INVALID, "rows must be 16-byte aligned");
-        if (v->n_rows && v->row_stride == 0) return fail(NEEDLE_ERR_INVALID, "row_stride is 0");
-    }
-    return NEEDLE_OK;
-}
-
-// Host batches: per-row lengths are readable here, so an oversized one is an argument error, not an out-of-bounds
-// read on the device (the kernels derive their chunk counts from the lengths and trust len <= row_stride).
-static int check_host_lengths(const needle_batch_view *v) {
-    if (!v->lengths) return NEEDLE_OK;
-    for (uint64_t r = 0; r < v->n_rows; ++r)
-        if (v->lengths[r] > v->row_stride) return fail(NEEDLE_ERR_INVALID, "lengths[r] > row_stride");
+    if ((v->row_stride * v->char_width) % 16 != 0)
+        return fail(NEEDLE_ERR_INVALID, "row_stride * char_width must be a multiple of 16 bytes for device batches");
+    if (((uintptr_t)v->rows) % 16 != 0) return fail(NEEDLE_ERR_INVALID, "rows must be 16-byte aligned");
+    if (v->n_rows && v->row_stride == 0) return fail(NEEDLE_ERR_INVALID, "row_stride is 0");
     return NEEDLE_OK;
 }
 
@@ -941,7 +931,7 @@ static int run_dev(const needle_pattern *cp, int op, const needle_batch_view *v,
                    bool packed8 = false) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, true);
+    int rc = check_view(v);
     if (rc) return rc;
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!d_bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
@@ -1195,246 +1185,7 @@ static int with_more_flag(hipStream_t stream, int *more, const char *what, Launc
     return NEEDLE_OK;
 }
 
-// Small host batches (above all the one-row batches of the Matcher mirror): one grow-only device arena + pinned
-// staging buffer + stream per host thread, ONE upload and ONE download per call -- instead of five hipMalloc/hipFree
-// pairs and as many synchronous copies.
-namespace {
-struct HostArena {
-    int dev = -1;
-    uint8_t *d = nullptr, *h = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    ~HostArena() { release(); }
-    void release() {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        if (stream) (void)hipStreamDestroy(stream);
-        d = h = nullptr;
-        stream = nullptr;
-        cap = 0;
-        dev = -1;
-    }
-    hipError_t reserve(size_t bytes) {
-        int cur = 0;
-        hipError_t e = hipGetDevice(&cur);
-        if (e != hipSuccess) return e;
-        if (cur == dev && bytes <= cap) return hipSuccess;
-        release();
-        size_t want = 1 << 16;
-        while (want < bytes) want <<= 1;
-        if ((e = hipMalloc((void **)&d, want)) != hipSuccess) return e;
-        if ((e = hipHostMalloc((void **)&h, want, hipHostMallocMapped)) != hipSuccess) return e;
-        if ((e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) != hipSuccess) return e;
-        cap = want;
-        dev = cur;
-        return hipSuccess;
-    }
-};
-constexpr size_t kSmallHostBatchBytes = 4u << 20;
-constexpr size_t kZeroCopyBytes = 16u << 10;
-} // namespace
-
-static int run_host_small(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t dst_stride, uint64_t *bitmap,
-                          int32_t *start, int32_t *end) {
-    static thread_local HostArena arena;
-    const size_t cw = v->char_width, n = (size_t)v->n_rows;
-    const size_t src_stride = (size_t)v->row_stride * cw;
-    const size_t words = (n + 63) / 64;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    // in: rows | lengths      out: bitmap | start | end
-    const size_t o_rows = 0, o_len = up16(n * dst_stride), in_bytes = o_len + (v->lengths ? up16(n * 4) : 0);
-    const size_t o_bm = in_bytes, o_s = o_bm + up16(words * 8), o_e = o_s + up16(n * 4), total = o_e + up16(n * 4);
-    HIP_TRY(arena.reserve(total));
-    if (dst_stride == src_stride) {
-        memcpy(arena.h + o_rows, v->rows, n * src_stride);
-    } else {
-        for (size_t r = 0; r < n; ++r) {
-            memcpy(arena.h + o_rows + r * dst_stride, (const uint8_t *)v->rows + r * src_stride, src_stride);
-            memset(arena.h + o_rows + r * dst_stride + src_stride, 0, dst_stride - src_stride);
-        }
-    }
-    if (v->lengths) memcpy(arena.h + o_len, v->lengths, n * 4);
-    // Tiny batches (one Matcher call): the kernel reads the pinned staging buffer and writes its results there
-    // directly over PCIe -- one launch and one wait, no copy commands at all.
-    const bool zero_copy = total <= kZeroCopyBytes;
-    uint8_t *base = arena.d;
-    if (zero_copy) {
-        void *mapped = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&mapped, arena.h, 0));
-        base = (uint8_t *)mapped;
-    } else {
-        HIP_TRY(hipMemcpyAsync(arena.d, arena.h, in_bytes, hipMemcpyHostToDevice, arena.stream));
-    }
-    needle_batch_view dv = *v;
-    dv.rows = base + o_rows;
-    dv.lengths = v->lengths ? (const uint32_t *)(base + o_len) : nullptr;
-    dv.row_stride = dst_stride / cw;
-    int rc = run_dev(p, op, &dv, (uint64_t *)(base + o_bm), (int32_t *)(base + o_s), (int32_t *)(base + o_e), arena.stream);
-    if (rc) return rc;
-    if (!zero_copy) {
-        const size_t out_bytes = op == OP_FIND ? total - o_bm : up16(words * 8);
-        HIP_TRY(hipMemcpyAsync(arena.h + o_bm, arena.d + o_bm, out_bytes, hipMemcpyDeviceToHost, arena.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(arena.stream));
-    memcpy(bitmap, arena.h + o_bm, words * 8);
-    if (op == OP_FIND) {
-        memcpy(start, arena.h + o_s, n * 4);
-        memcpy(end, arena.h + o_e, n * 4);
-    }
-    return NEEDLE_OK;
-}
-
-// The device allocations of one host convenience call: whatever it holds is freed on every return path.
-struct DevAllocs {
-    std::vector<void *> held;
-    DevAllocs() = default;
-    DevAllocs(const DevAllocs &) = delete;
-    DevAllocs &operator=(const DevAllocs &) = delete;
-    ~DevAllocs() {
-        for (void *q : held) (void)hipFree(q);
-    }
-    template <class T>
-    hipError_t alloc(T **out, size_t bytes) {
-        const hipError_t e = hipMalloc((void **)out, bytes);
-        if (e == hipSuccess) held.push_back((void *)*out);
-        return e;
-    }
-};
-
-// The rows of a host batch on the device, padded to a stride of whole 16 bytes (zero-filled), and their lengths (d_len: not used without
-// lengths).  *dv: the batch as a device view.
-static uint64_t padded_stride_bytes(const needle_batch_view *v) { return std::max<uint64_t>(16, (v->row_stride * v->char_width + 15) & ~(uint64_t)15); }
-static hipError_t upload_rows(const needle_batch_view *v, void *d_rows, uint32_t *d_len, needle_batch_view *dv) {
-    const uint64_t src_stride = v->row_stride * v->char_width, dst_stride = padded_stride_bytes(v);
-    hipError_t e = hipSuccess;
-    if (dst_stride == src_stride) {
-        e = hipMemcpy(d_rows, v->rows, v->n_rows * src_stride, hipMemcpyHostToDevice);
-    } else {
-        e = hipMemset(d_rows, 0, v->n_rows * dst_stride);
-        if (e == hipSuccess && src_stride) e = hipMemcpy2D(d_rows, dst_stride, v->rows, src_stride, src_stride, v->n_rows, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && v->lengths) e = hipMemcpy(d_len, v->lengths, v->n_rows * 4, hipMemcpyHostToDevice);
-    *dv = *v;
-    dv->rows = d_rows;
-    dv->lengths = v->lengths ? d_len : nullptr;
-    dv->row_stride = dst_stride / v->char_width;
-    return e;
-}
-
-// NEEDLE_HOST_CHUNK_BYTES: what the host entry points keep resident on the device at a time (tests shrink it).
-static uint64_t host_chunk_bytes() {
-    static const uint64_t v = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
-    return v;
-}
-// NEEDLE_HOST_RESULT_BYTES: the bound on the find-all results the host entry points keep resident on the device at a time (tests shrink it).
-static uint64_t host_result_bytes() {
-    static const uint64_t v = getenv("NEEDLE_HOST_RESULT_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_RESULT_BYTES")) : (512ull << 20);
-    return v;
-}
-
-// The fill pass of the CSR host entries over rows [r0, r1), whose counts stand summed up in `offsets`.  It runs over sub-ranges of the rows so
-// that the results resident on the device stay bounded too (NEEDLE_HOST_RESULT_BYTES): a dense-match batch (a one-char pattern over
-// 256-char rows files ~2 KiB per row) would otherwise ask for several times the chunk's row bytes in one allocation.
-// fill(a, n, d_csr, d_start, d_end, &more): the layout's fill of rows [a, a + n) at the sub-range's own offsets, uploaded to d_csr.
-template <class Fill>
-static int csr_fill_pass(const std::string &who, const uint64_t *offsets, uint64_t r0, uint64_t r1, uint8_t *d_csr, int32_t *start, int32_t *end,
-                         DevAllocs &dev, Fill &&fill) {
-    const uint64_t max_m = std::max<uint64_t>(host_result_bytes() / 8, 1);
-    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    std::vector<std::pair<uint64_t, uint64_t>> ranges; // [a, b): at least one row, at most max_m matches (one row may exceed it)
-    uint64_t biggest = 0;
-    for (uint64_t a = r0; a < r1;) {
-        uint64_t b = a + 1;
-        while (b < r1 && offsets[b + 1] - offsets[a] <= max_m) ++b;
-        ranges.emplace_back(a, b);
-        biggest = std::max<uint64_t>(biggest, offsets[b] - offsets[a]);
-        a = b;
-    }
-    uint8_t *d_out = nullptr; // start | end
-    hipError_t e = dev.alloc(&d_out, 2 * up16(biggest * 4) + 16);
-    if (e != hipSuccess) return hip_fail(e, (who + " results").c_str());
-    std::vector<uint64_t> local;
-    for (const auto &rg : ranges) {
-        const uint64_t a = rg.first, sn = rg.second - rg.first, m = offsets[rg.second] - offsets[a];
-        if (m == 0) continue;
-        local.resize(sn + 1);
-        for (uint64_t r = 0; r <= sn; ++r) local[r] = offsets[a + r] - offsets[a];
-        e = hipMemcpy(d_csr, local.data(), (sn + 1) * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, (who + " offsets").c_str());
-        int more = 0;
-        int rc = fill(a, sn, (const uint64_t *)d_csr, (int32_t *)d_out, (int32_t *)(d_out + up16(biggest * 4)), &more);
-        if (rc) return rc;
-        if (more) return fail(NEEDLE_ERR_DEVICE, who + ": count pass and fill pass disagree");
-        e = hipMemcpy(start + offsets[a], d_out, m * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(end + offsets[a], d_out + up16(biggest * 4), m * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, (who + " download").c_str());
-    }
-    return NEEDLE_OK;
-}
-
-// Host batches of any size: run(chunk, r0) for consecutive row chunks of at most NEEDLE_HOST_CHUNK_BYTES on the device -- a row costs its
-// padded text + per_row bytes there -- that start on 64-row boundaries, so every chunk owns whole bitmap words.
-template <class Run>
-static int for_host_chunks(const needle_batch_view *v, uint64_t per_row, Run &&run) {
-    const uint64_t per = std::max<uint64_t>(64, (host_chunk_bytes() / (padded_stride_bytes(v) + per_row)) & ~(uint64_t)63);
-    for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
-        needle_batch_view c = *v;
-        c.n_rows = std::min<uint64_t>(per, v->n_rows - r0);
-        c.rows = (const uint8_t *)v->rows + r0 * v->row_stride * v->char_width;
-        c.lengths = v->lengths ? v->lengths + r0 : nullptr;
-        int rc = run(c, r0);
-        if (rc) return rc;
-    }
-    return NEEDLE_OK;
-}
-
-// Host-buffer convenience: pad rows to a 16-byte stride, upload, run, download.
-static int run_host_one(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t *bitmap, int32_t *start,
-                        int32_t *end) {
-    int rc = check_view(v, false);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
-    const uint64_t dst_stride = padded_stride_bytes(v);
-    const size_t words = (v->n_rows + 63) / 64;
-    if (op == OP_FIND && (!start || !end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
-    if (v->n_rows * dst_stride + v->n_rows * 16 <= kSmallHostBatchBytes) return run_host_small(p, op, v, dst_stride, bitmap, start, end);
-    DevAllocs dev;
-    uint8_t *d_rows = nullptr;
-    uint32_t *d_len = nullptr;
-    uint64_t *d_bm = nullptr;
-    int32_t *d_s = nullptr, *d_e = nullptr;
-    needle_batch_view dv;
-    HIP_TRY(dev.alloc(&d_rows, v->n_rows * dst_stride));
-    if (v->lengths) HIP_TRY(dev.alloc(&d_len, v->n_rows * 4));
-    HIP_TRY(upload_rows(v, d_rows, d_len, &dv));
-    HIP_TRY(dev.alloc(&d_bm, words * 8));
-    if (op == OP_FIND) {
-        HIP_TRY(dev.alloc(&d_s, v->n_rows * 4));
-        HIP_TRY(dev.alloc(&d_e, v->n_rows * 4));
-    }
-    rc = run_dev(p, op, &dv, d_bm, d_s, d_e, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(bitmap, d_bm, words * 8, hipMemcpyDeviceToHost));
-    if (op == OP_FIND) {
-        HIP_TRY(hipMemcpy(start, d_s, v->n_rows * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(end, d_e, v->n_rows * 4, hipMemcpyDeviceToHost));
-    }
-    return NEEDLE_OK;
-}
-
-static int run_host(const needle_pattern *p, int op, const needle_batch_view *v, uint64_t *bitmap, int32_t *start,
-                    int32_t *end) {
-    int rc = check_view(v, false);
-    if (rc) return rc;
-    if ((rc = check_host_lengths(v))) return rc;
-    return for_host_chunks(v, 0, [&](const needle_batch_view &c, uint64_t r0) {
-        return run_host_one(p, op, &c, bitmap ? bitmap + r0 / 64 : nullptr, start ? start + r0 : nullptr, end ? end + r0 : nullptr);
-    });
-}
-
-static int check_packed(const needle_packed_view *v) {
+int needle::check_packed(const needle_packed_view *v) {
     if (!v) return fail(NEEDLE_ERR_INVALID, "packed view is NULL");
     if (v->char_width != 1 && v->char_width != 2) return fail(NEEDLE_ERR_INVALID, "char_width must be 1 or 2");
     if (!v->offsets) return fail(NEEDLE_ERR_INVALID, "offsets is NULL");
@@ -1446,132 +1197,6 @@ static int check_packed_dev(const needle_pattern *p, const needle_packed_view *v
     int rc = check_packed(v);
     if (rc) return rc;
     if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
-    return NEEDLE_OK;
-}
-
-// The offsets of a packed HOST batch (readable here): non-decreasing; *max_len = its longest row, in chars.
-static int check_packed_host_offsets(const needle_packed_view *v, uint64_t *max_len) {
-    *max_len = 0;
-    for (uint64_t r = 0; r < v->n_rows; ++r) {
-        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
-        *max_len = std::max<uint64_t>(*max_len, v->offsets[r + 1] - v->offsets[r]);
-    }
-    return NEEDLE_OK;
-}
-
-// One packed host batch (checked by run_packed_host: rows of up to max_len chars) as fixed-stride rows: upload, unpack on the device, run, download.
-static int run_packed_host_one(const needle_pattern *p, int op, const needle_packed_view *v, uint64_t max_len, uint64_t *bitmap,
-                               int32_t *start, int32_t *end) {
-    const uint64_t cw = v->char_width;
-    if (max_len > 0xFFFFFFFFull) return fail(NEEDLE_ERR_INVALID, "row longer than 2^32 - 1 chars");
-    const uint64_t total_chars = v->offsets[v->n_rows];
-    if (total_chars && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    uint64_t stride_bytes = (max_len * cw + 15) & ~(uint64_t)15;
-    if (stride_bytes == 0) stride_bytes = 16;
-    const size_t words = (v->n_rows + 63) / 64;
-    DevAllocs dev;
-    void *d_data = nullptr, *d_rows = nullptr;
-    uint64_t *d_off = nullptr, *d_bm = nullptr;
-    uint32_t *d_len = nullptr;
-    int32_t *d_s = nullptr, *d_e = nullptr;
-    const size_t data_bytes = (size_t)((total_chars * cw + 3) & ~(uint64_t)3);
-    HIP_TRY(dev.alloc(&d_data, data_bytes ? data_bytes : 4));
-    if (total_chars) HIP_TRY(hipMemcpy(d_data, v->data, (size_t)(total_chars * cw), hipMemcpyHostToDevice));
-    HIP_TRY(dev.alloc(&d_off, (v->n_rows + 1) * 8));
-    HIP_TRY(hipMemcpy(d_off, v->offsets, (v->n_rows + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(dev.alloc(&d_rows, v->n_rows * stride_bytes));
-    HIP_TRY(dev.alloc(&d_len, v->n_rows * 4));
-    HIP_TRY(dev.alloc(&d_bm, words * 8));
-    if (op == OP_FIND) {
-        HIP_TRY(dev.alloc(&d_s, v->n_rows * 4));
-        HIP_TRY(dev.alloc(&d_e, v->n_rows * 4));
-    }
-    needle_packed_view dpv = *v;
-    dpv.data = d_data;
-    dpv.offsets = d_off;
-    int rc = needle_rows_from_packed_dev(&dpv, d_rows, stride_bytes / cw, d_len, nullptr, nullptr);
-    if (rc) return rc;
-    needle_batch_view bv;
-    memset(&bv, 0, sizeof(bv));
-    bv.rows = d_rows;
-    bv.char_width = v->char_width;
-    bv.n_rows = v->n_rows;
-    bv.row_stride = stride_bytes / cw;
-    bv.lengths = d_len;
-    rc = run_dev(p, op, &bv, d_bm, d_s, d_e, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(bitmap, d_bm, words * 8, hipMemcpyDeviceToHost));
-    if (op == OP_FIND) {
-        HIP_TRY(hipMemcpy(start, d_s, v->n_rows * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(end, d_e, v->n_rows * 4, hipMemcpyDeviceToHost));
-    }
-    return NEEDLE_OK;
-}
-
-// Packed host batch.  The fixed-stride layout the kernels read pads every row to the longest one: harmless when the
-// lengths are alike, ruinous when one 1 MB document sits among a million 40-char strings.  Rows are therefore grouped
-// into length classes (stride 64 B, 256 B, 1 KiB, ... x4) and every class runs as its own batch, so the padded
-// bytes stay below 4x the text.
-static int run_packed_host(const needle_pattern *p, int op, const needle_packed_view *v, uint64_t *bitmap, int32_t *start,
-                           int32_t *end) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
-    if (op == OP_FIND && (!start || !end)) return fail(NEEDLE_ERR_INVALID, "start/end is NULL");
-    const uint64_t cw = v->char_width, n = v->n_rows;
-    uint64_t max_len = 0;
-    if ((rc = check_packed_host_offsets(v, &max_len))) return rc;
-    if (v->offsets[n] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    const uint64_t total_bytes = v->offsets[n] * cw;
-    const uint64_t padded = n * std::max<uint64_t>(16, (max_len * cw + 15) & ~(uint64_t)15);
-    if (padded <= 4 * total_bytes + (64u << 10)) return run_packed_host_one(p, op, v, max_len, bitmap, start, end);
-    auto klass = [&](uint64_t len_chars) { // smallest k with len * cw <= 64 << 2k
-        int k = 0;
-        while ((len_chars * cw) > (64ull << (2 * k))) ++k;
-        return k;
-    };
-    const int n_classes = klass(max_len) + 1;
-    std::vector<std::vector<uint64_t>> rows_of((size_t)n_classes);
-    for (uint64_t r = 0; r < n; ++r) rows_of[(size_t)klass(v->offsets[r + 1] - v->offsets[r])].push_back(r);
-    memset(bitmap, 0, ((n + 63) / 64) * 8);
-    std::vector<uint8_t> data;
-    std::vector<uint64_t> off, bm;
-    std::vector<int32_t> st, en;
-    for (const auto &ids : rows_of) {
-        if (ids.empty()) continue;
-        off.assign(ids.size() + 1, 0);
-        uint64_t longest = 0;
-        for (size_t i = 0; i < ids.size(); ++i) {
-            const uint64_t len = v->offsets[ids[i] + 1] - v->offsets[ids[i]];
-            off[i + 1] = off[i] + len;
-            longest = std::max(longest, len);
-        }
-        data.resize((size_t)(off.back() * cw));
-        for (size_t i = 0; i < ids.size(); ++i)
-            memcpy(data.data() + off[i] * cw, (const uint8_t *)v->data + v->offsets[ids[i]] * cw, (size_t)((off[i + 1] - off[i]) * cw));
-        needle_packed_view sub;
-        sub.data = data.data();
-        sub.char_width = v->char_width;
-        sub.n_rows = ids.size();
-        sub.offsets = off.data();
-        bm.assign((ids.size() + 63) / 64, 0);
-        if (op == OP_FIND) {
-            st.assign(ids.size(), -1);
-            en.assign(ids.size(), -1);
-        }
-        rc = run_packed_host_one(p, op, &sub, longest, bm.data(), st.data(), en.data());
-        if (rc) return rc;
-        for (size_t i = 0; i < ids.size(); ++i) {
-            if ((bm[i >> 6] >> (i & 63)) & 1) bitmap[ids[i] >> 6] |= 1ull << (ids[i] & 63);
-            if (op == OP_FIND) {
-                start[ids[i]] = st[i];
-                end[ids[i]] = en[i];
-            }
-        }
-    }
     return NEEDLE_OK;
 }
 
@@ -1894,152 +1519,6 @@ int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_
 
 } // extern "C"
 
-// The chunking of the packed HOST entries (needle_find_all_csr_packed_host, needle_find_packed{16,8}_packed_host): consecutive rows
-// [r0, r1), at least `align` rows (or the rest), grown `align` rows at a time while the chunk's text + per_row bytes per row stay within
-// NEEDLE_HOST_CHUNK_BYTES.
-static std::vector<std::pair<uint64_t, uint64_t>> packed_host_chunks(const needle_packed_view *v, uint64_t per_row, uint64_t align) {
-    const uint64_t n = v->n_rows, cw = v->char_width;
-    auto cost = [&](uint64_t r0, uint64_t r1) { return (v->offsets[r1] - v->offsets[r0]) * cw + (r1 - r0) * per_row; };
-    std::vector<std::pair<uint64_t, uint64_t>> chunks;
-    for (uint64_t r0 = 0; r0 < n;) {
-        uint64_t r1 = std::min<uint64_t>(r0 + align, n);
-        while (r1 < n && cost(r0, std::min<uint64_t>(r1 + align, n)) <= host_chunk_bytes()) r1 = std::min<uint64_t>(r1 + align, n);
-        chunks.emplace_back(r0, r1);
-        r0 = r1;
-    }
-    return chunks;
-}
-
-// Upload chunk [r0, r1) of a packed host batch: its text to d_data, its offsets rebased to the chunk's first char to d_offsets (the
-// caller's own when that is char 0; `local` holds the rebased copy).  *dv: the chunk as a device view.
-static hipError_t upload_packed_chunk(const needle_packed_view *v, uint64_t r0, uint64_t r1, uint8_t *d_data, uint64_t *d_offsets,
-                                      std::vector<uint64_t> &local, needle_packed_view *dv) {
-    const uint64_t nr = r1 - r0, cw = v->char_width, c0 = v->offsets[r0], text = (v->offsets[r1] - c0) * cw;
-    const uint64_t *off = v->offsets + r0;
-    if (c0) {
-        local.resize(nr + 1);
-        for (uint64_t r = 0; r <= nr; ++r) local[r] = v->offsets[r0 + r] - c0;
-        off = local.data();
-    }
-    hipError_t e = text ? hipMemcpy(d_data, (const uint8_t *)v->data + c0 * cw, text, hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpy(d_offsets, off, (nr + 1) * 8, hipMemcpyHostToDevice);
-    *dv = *v;
-    dv->data = d_data;
-    dv->offsets = d_offsets;
-    dv->n_rows = nr;
-    return e;
-}
-
-extern "C" {
-
-// The packed batch in host memory: row chunks of at most NEEDLE_HOST_CHUNK_BYTES of text are uploaded (their offsets rebased to the
-// chunk), counted, the prefix sum built here, filled (in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of results) and downloaded.
-int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
-                                    uint64_t capacity, uint64_t *total) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (!offsets || !total || (capacity && (!start || !end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    offsets[0] = 0;
-    *total = 0;
-    const uint64_t n = v->n_rows, cw = v->char_width;
-    if (n == 0) return NEEDLE_OK;
-    uint64_t max_len = 0;
-    if ((rc = check_packed_host_offsets(v, &max_len))) return rc;
-    if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    std::vector<uint64_t> local;
-    std::vector<uint32_t> counts;
-    for (const auto &chunk : packed_host_chunks(v, 12, 1)) { // (12 bytes per row: offset + count)
-        const uint64_t r0 = chunk.first, r1 = chunk.second, nr = r1 - r0, text = (v->offsets[r1] - v->offsets[r0]) * cw;
-        DevAllocs dev;
-        uint8_t *d = nullptr; // data | offsets | counts | CSR offsets
-        const uint64_t o_off = up16(std::max<uint64_t>(text, 4)), o_cnt = o_off + up16((nr + 1) * 8), o_csr = o_cnt + up16(nr * 4),
-                       all = o_csr + up16((nr + 1) * 8);
-        HIP_TRY(dev.alloc(&d, all));
-        needle_packed_view dv;
-        hipError_t e = upload_packed_chunk(v, r0, r1, d, (uint64_t *)(d + o_off), local, &dv);
-        if (e != hipSuccess) return hip_fail(e, "find_all_csr_packed_host upload");
-        rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(d + o_cnt), nullptr);
-        if (rc) return rc;
-        counts.resize(nr);
-        e = hipMemcpy(counts.data(), d + o_cnt, nr * 4, hipMemcpyDeviceToHost); // (synchronises with the count pass)
-        if (e != hipSuccess) return hip_fail(e, "find_all_csr_packed_host counts");
-        for (uint64_t r = 0; r < nr; ++r) offsets[r0 + r + 1] = offsets[r0 + r] + counts[r];
-        if (offsets[r1] > offsets[r0] && offsets[r1] <= capacity) {
-            rc = csr_fill_pass("find_all_csr_packed_host", offsets, r0, r1, d + o_csr, start, end, dev,
-                               [&](uint64_t a, uint64_t sn, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
-                                   needle_packed_view sv = dv;
-                                   sv.offsets = dv.offsets + (a - r0);
-                                   sv.n_rows = sn;
-                                   return needle_find_all_csr_packed_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
-                               });
-            if (rc) return rc;
-        }
-    }
-    *total = offsets[n];
-    return NEEDLE_OK;
-}
-
-} // extern "C"
-
-// needle_find_packed{16,8}_packed_host: the offsets checked on the host (a row beyond the form: NEEDLE_ERR_UNSUPPORTED before any
-// device call), then chunks of whole 64-row groups (the bitmap words stay the caller's) of at most NEEDLE_HOST_CHUNK_BYTES of text
-// uploaded with their offsets rebased to the chunk, scanned by needle_find_packed{16,8}_packed_dev where they lie and downloaded --
-// one chunk after the other, no overlap of one chunk's upload with the previous chunk's scan.
-static int run_packed_compact_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, void *out, bool packed8) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap || !out) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    const uint64_t n = v->n_rows, cw = v->char_width, limit = packed8 ? 256 : 65534, rb = packed8 ? 2 : 4;
-    for (uint64_t r = 0; r < n; ++r) {
-        if (v->offsets[r + 1] < v->offsets[r]) return fail(NEEDLE_ERR_INVALID, "offsets must be non-decreasing");
-        if (v->offsets[r + 1] - v->offsets[r] > limit)
-            return fail(NEEDLE_ERR_UNSUPPORTED, packed8 ? "8-bit start / length: rows of at most 256 chars (use needle_find_packed16_packed_host)"
-                                                        : "16-bit offsets: rows of at most 65 534 chars (use needle_find_packed_host)");
-    }
-    if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    // whole 64-row groups per chunk (the bitmap words stay the caller's): text + offset + result per row within the budget
-    const std::vector<std::pair<uint64_t, uint64_t>> chunks = packed_host_chunks(v, 8 + rb, 64);
-    uint64_t biggest = 0, max_rows = 0;
-    for (const auto &c : chunks) {
-        biggest = std::max<uint64_t>(biggest, up16(std::max<uint64_t>((v->offsets[c.second] - v->offsets[c.first]) * cw, 4)));
-        max_rows = std::max<uint64_t>(max_rows, c.second - c.first);
-    }
-    // data | offsets | bitmap | results (one buffer for every chunk)
-    const uint64_t o_off = biggest, o_bm = o_off + up16((max_rows + 1) * 8), o_res = o_bm + up16(((max_rows + 63) / 64) * 8),
-                   all = o_res + up16(max_rows * rb);
-    DevAllocs dev;
-    uint8_t *d = nullptr;
-    HIP_TRY(dev.alloc(&d, all));
-    std::vector<uint64_t> local;
-    for (const auto &c : chunks) {
-        const uint64_t r0 = c.first, nr = c.second - c.first;
-        needle_packed_view dv;
-        hipError_t e = upload_packed_chunk(v, r0, c.second, d, (uint64_t *)(d + o_off), local, &dv);
-        if (e != hipSuccess) return hip_fail(e, "find_packed_packed_host upload");
-        rc = packed8 ? needle_find_packed8_packed_dev(p, &dv, (uint64_t *)(d + o_bm), (uint16_t *)(d + o_res), nullptr, nullptr)
-                     : needle_find_packed16_packed_dev(p, &dv, (uint64_t *)(d + o_bm), (uint32_t *)(d + o_res), nullptr, nullptr);
-        if (rc) return rc;
-        e = hipMemcpy(bitmap + r0 / 64, d + o_bm, ((nr + 63) / 64) * 8, hipMemcpyDeviceToHost); // (synchronises with the scan)
-        if (e == hipSuccess) e = hipMemcpy((uint8_t *)out + r0 * rb, d + o_res, nr * rb, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "find_packed_packed_host download");
-    }
-    return NEEDLE_OK;
-}
-
-extern "C" {
-int needle_find_packed16_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, uint32_t *start_end16) {
-    return run_packed_compact_host(p, v, bitmap, start_end16, false);
-}
-int needle_find_packed8_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, uint16_t *start_len8) {
-    return run_packed_compact_host(p, v, bitmap, start_len8, true);
-}
-} // extern "C"
-
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -2085,16 +1564,6 @@ int needle_rows_from_packed_dev(const needle_packed_view *v, void *d_rows, uint6
     HIP_TRY(launch_unpack(v->data, v->offsets, v->n_rows, v->char_width, d_rows, stride_bytes, d_lengths, d_overflow,
                           cus, (hipStream_t)stream));
     return NEEDLE_OK;
-}
-
-int needle_matches_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm) {
-    return run_packed_host(p, OP_MATCHES, v, bm, nullptr, nullptr);
-}
-int needle_contained_in_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm) {
-    return run_packed_host(p, OP_CONTAINED_IN, v, bm, nullptr, nullptr);
-}
-int needle_find_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bm, int32_t *st, int32_t *en) {
-    return run_packed_host(p, OP_FIND, v, bm, st, en);
 }
 
 const char *needle_version(void) { return "needle_hip 0.1 (gfx950)"; }
@@ -2591,10 +2060,6 @@ int needle_find_next_dev(const needle_pattern *p, const needle_batch_view *v, co
 }
 // The round-per-match form: one needle_find_next pass over the batch per round, one stream synchronisation per round.
 // Rows of 64 MiB and more (stripe paths only) take it; NEEDLE_FIND_ALL_ROUNDS=1 forces it (tests cross-check the two).
-static bool find_all_rounds_forced() {
-    static const bool forced = (getenv("NEEDLE_FIND_ALL_ROUNDS") ? atoi(getenv("NEEDLE_FIND_ALL_ROUNDS")) : 0) != 0;
-    return forced;
-}
 static int find_all_rounds(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *d_counts, int32_t *d_start,
                            int32_t *d_end, int *more, hipStream_t stream) {
     const size_t n = (size_t)v->n_rows, words = (n + 63) / 64;
@@ -2714,7 +2179,7 @@ int needle_find_all_dev(const needle_pattern *cp, const needle_batch_view *v, ui
                         int32_t *d_end, int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, true);
+    int rc = check_view(v);
     if (rc) return rc;
     if (more) *more = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
@@ -2729,7 +2194,7 @@ int needle_find_all_packed16_dev(const needle_pattern *cp, const needle_batch_vi
                                  uint32_t *d_start_end16, int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, true);
+    int rc = check_view(v);
     if (rc) return rc;
     if (more) *more = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
@@ -2743,7 +2208,7 @@ int needle_find_all_blocked16_dev(const needle_pattern *cp, const needle_batch_v
                                   uint32_t *d_blocks, int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, true);
+    int rc = check_view(v);
     if (rc) return rc;
     if (more) *more = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
@@ -2755,7 +2220,7 @@ int needle_find_all_blocked16_dev(const needle_pattern *cp, const needle_batch_v
 int needle_count_matches_dev(const needle_pattern *cp, const needle_batch_view *v, uint32_t *d_counts, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, true);
+    int rc = check_view(v);
     if (rc) return rc;
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!d_counts) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
@@ -2766,243 +2231,13 @@ int needle_find_all_csr_dev(const needle_pattern *cp, const needle_batch_view *v
                             int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, true);
+    int rc = check_view(v);
     if (rc) return rc;
     if (more) *more = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
     if (!d_offsets || !d_start || !d_end) return fail(NEEDLE_ERR_INVALID, "offsets / output buffer is NULL");
     return find_all_one_pass(p, v, 0, nullptr, d_start, d_end, d_offsets, false, more, (hipStream_t)stream_);
 }
-
-// start_end16 != nullptr: the one-dword-per-match form (needle_find_all_packed16_dev) -- start / end are not used
-static int find_all_host_one(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts, int32_t *start,
-                             int32_t *end, int *more, uint32_t *start_end16 = nullptr) {
-    const size_t n = (size_t)v->n_rows, dst_stride = (size_t)padded_stride_bytes(v);
-    uint8_t *d = nullptr; // rows | lengths | counts | start | end
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_len = up16(n * dst_stride), o_cnt = o_len + up16(n * 4), o_s = o_cnt + up16(n * 4);
-    const size_t o_e = o_s + up16(n * slots * 4), total = o_e + (start_end16 ? 0 : up16(n * slots * 4));
-    DevAllocs dev;
-    HIP_TRY(dev.alloc(&d, total));
-    needle_batch_view dv;
-    hipError_t e = upload_rows(v, d, (uint32_t *)(d + o_len), &dv);
-    if (e == hipSuccess && slots) e = hipMemset(d + o_s, 0xFF, total - o_s); // -1 in every slot
-    if (e != hipSuccess) return hip_fail(e, "find_all_host upload");
-    int rc = start_end16 ? needle_find_all_packed16_dev(p, &dv, slots, (uint32_t *)(d + o_cnt), (uint32_t *)(d + o_s), more, nullptr)
-                         : needle_find_all_dev(p, &dv, slots, (uint32_t *)(d + o_cnt), (int32_t *)(d + o_s), (int32_t *)(d + o_e), more, nullptr);
-    if (rc) return rc;
-    e = hipMemcpy(counts, d + o_cnt, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && slots) e = hipMemcpy(start_end16 ? (void *)start_end16 : (void *)start, d + o_s, n * slots * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && slots && !start_end16) e = hipMemcpy(end, d + o_e, n * slots * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "find_all_host download");
-    return NEEDLE_OK;
-}
-
-// (like the other host entry points: at most ~2 GiB of rows + results resident on the device at a time)
-// One chunk of needle_find_all_csr_host: upload, count pass, prefix sum on the host (the counts come back anyway), fill
-// pass while the rows are still resident, download.  offsets: n + 1 entries, offsets[0] given by the caller.
-static int find_all_csr_host_one(const needle_pattern *p, const needle_batch_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
-                                 uint64_t capacity) {
-    const size_t n = (size_t)v->n_rows, dst_stride = (size_t)padded_stride_bytes(v);
-    uint8_t *d = nullptr; // rows | lengths | counts | offsets
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_len = up16(n * dst_stride), o_cnt = o_len + up16(n * 4), o_off = o_cnt + up16(n * 4), total = o_off + up16((n + 1) * 8);
-    DevAllocs dev;
-    HIP_TRY(dev.alloc(&d, total));
-    needle_batch_view dv;
-    hipError_t e = upload_rows(v, d, (uint32_t *)(d + o_len), &dv);
-    if (e != hipSuccess) return hip_fail(e, "find_all_csr_host upload");
-    int rc = needle_count_matches_dev(p, &dv, (uint32_t *)(d + o_cnt), nullptr);
-    if (rc) return rc;
-    std::vector<uint32_t> counts(n);
-    e = hipMemcpy(counts.data(), d + o_cnt, n * 4, hipMemcpyDeviceToHost); // (synchronises with the count pass)
-    if (e != hipSuccess) return hip_fail(e, "find_all_csr_host counts");
-    for (size_t r = 0; r < n; ++r) offsets[r + 1] = offsets[r] + counts[r];
-    const uint64_t m = offsets[n] - offsets[0];
-    if (m == 0 || offsets[n] > capacity) return NEEDLE_OK; // nothing to file, or the caller's buffers are too small
-    return csr_fill_pass("find_all_csr_host", offsets, 0, n, d + o_off, start, end, dev,
-                         [&](uint64_t r0, uint64_t nr, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
-                             needle_batch_view sv = dv;
-                             sv.rows = d + r0 * dst_stride;
-                             sv.lengths = dv.lengths ? dv.lengths + r0 : nullptr;
-                             sv.n_rows = nr;
-                             return needle_find_all_csr_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
-                         });
-}
-int needle_find_all_csr_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
-                             uint64_t capacity, uint64_t *total) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, false);
-    if (rc) return rc;
-    if ((rc = check_host_lengths(v))) return rc;
-    if (!offsets || !total || (capacity && (!start || !end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    offsets[0] = 0;
-    *total = 0;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    rc = for_host_chunks(v, 16, [&](const needle_batch_view &c, uint64_t r0) { return find_all_csr_host_one(p, &c, offsets + r0, start, end, capacity); });
-    if (rc == NEEDLE_OK) *total = offsets[v->n_rows];
-    return rc;
-}
-static int find_all_host(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts, int32_t *start,
-                         int32_t *end, int *more, uint32_t *start_end16) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_view(v, false);
-    if (rc) return rc;
-    if ((rc = check_host_lengths(v))) return rc;
-    if (more) *more = 0;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!counts || (slots && !start_end16 && (!start || !end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    // (rows of at most 65 534 chars: an empty match at index 65 535 would read as an unfiled slot; NEEDLE_FIND_ALL_ROUNDS: the tests'
-    // cross-check of the round-per-match form goes through needle_find_all_dev)
-    const bool packed_inside = !find_all_rounds_forced() && (v->lengths ? v->row_stride : v->row_len) <= 65534u; // (lengths[r] <= row_stride: checked above)
-    std::vector<uint32_t> stage;
-    return for_host_chunks(v, 8 + 8ull * slots, [&](const needle_batch_view &c, uint64_t r0) {
-        int m = 0, rc = NEEDLE_OK;
-        if (!start_end16 && slots && packed_inside) {
-            // int32 results wanted, rows of at most 65 535 chars: the one-dword form on the device and over PCIe (half the result
-            // bytes both ways), opened into the caller's two arrays here on the host
-            stage.resize((size_t)c.n_rows * slots);
-            rc = find_all_host_one(p, &c, slots, counts + r0, nullptr, nullptr, &m, stage.data());
-            if (rc) return rc;
-            int32_t *so = start + r0 * slots, *eo = end + r0 * slots;
-            for (size_t i = 0; i < stage.size(); ++i) {
-                const uint32_t w = stage[i];
-                const bool none = w == 0xFFFFFFFFu; // an unfiled slot (a real match has start <= end, never 0xFFFF | 0xFFFF << 16)
-                so[i] = none ? -1 : (int32_t)(w & 0xFFFFu);
-                eo[i] = none ? -1 : (int32_t)(w >> 16);
-            }
-        } else {
-            rc = find_all_host_one(p, &c, slots, counts + r0, start ? start + r0 * slots : nullptr, end ? end + r0 * slots : nullptr, &m,
-                                   start_end16 ? start_end16 + r0 * slots : nullptr);
-            if (rc) return rc;
-        }
-        if (m && more) *more = 1;
-        return (int)NEEDLE_OK;
-    });
-}
-int needle_find_all_host(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts, int32_t *start,
-                         int32_t *end, int *more) {
-    return find_all_host(p, v, slots, counts, start, end, more, nullptr);
-}
-int needle_find_all_packed16_host(const needle_pattern *p, const needle_batch_view *v, uint32_t slots, uint32_t *counts,
-                                  uint32_t *start_end16, int *more) {
-    if (slots && !start_end16) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    if (v && (v->lengths ? v->row_stride : v->row_len) > 65535u) // (the caller's stride, before any padding; lengths[r] <= row_stride is checked below)
-        return fail(NEEDLE_ERR_UNSUPPORTED, "16-bit start / end: rows of at most 65535 chars");
-    static uint32_t none = 0; // (slots == 0: counting only; a non-null marker keeps the packed form)
-    return find_all_host(p, v, slots, counts, nullptr, nullptr, more, start_end16 ? start_end16 : &none);
-}
-int needle_matches_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bm) {
-    return run_host(p, OP_MATCHES, v, bm, nullptr, nullptr);
-}
-int needle_contained_in_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bm) {
-    return run_host(p, OP_CONTAINED_IN, v, bm, nullptr, nullptr);
-}
-int needle_find_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bm, int32_t *st, int32_t *en) {
-    return run_host(p, OP_FIND, v, bm, st, en);
-}
-
-} // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Matcher mirror: fields as the generated class declares them (DFAClassBuilder.addFields :688-699); the
-// constructor leaves them at the JVM default 0 (the generated <init> only stores string and length).
-struct needle_matcher {
-    const needle_pattern *p;
-    std::vector<uint16_t> s;
-    int next_start = 0, start = 0, end = 0;
-};
-
-static int one_row(const needle_matcher *m, int op, int from, int *matched, int *st, int *en) {
-    const size_t n = m->s.size() - (size_t)from;
-    needle_batch_view v;
-    memset(&v, 0, sizeof(v));
-    v.rows = n ? (const void *)(m->s.data() + from) : (const void *)&v; // never read when n == 0
-    v.char_width = 2;
-    v.n_rows = 1;
-    v.row_stride = n;
-    v.row_len = (uint32_t)n;
-    uint64_t bm = 0;
-    int32_t s32 = -1, e32 = -1;
-    int rc = run_host(m->p, op, &v, &bm, &s32, &e32);
-    if (rc) return rc;
-    *matched = (int)(bm & 1);
-    if (st) *st = s32;
-    if (en) *en = e32;
-    return NEEDLE_OK;
-}
-
-extern "C" {
-
-int needle_matcher_create(const needle_pattern *p, const uint16_t *s, size_t n, needle_matcher **out) {
-    if (!p || !out || (!s && n)) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    needle_matcher *m = new needle_matcher();
-    m->p = p;
-    m->s.assign(s, s + n);
-    *out = m;
-    return NEEDLE_OK;
-}
-
-void needle_matcher_destroy(needle_matcher *m) { delete m; }
-
-int needle_matcher_matches(needle_matcher *m, int *r) {
-    if (!m || !r) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    return one_row(m, OP_MATCHES, 0, r, nullptr, nullptr);
-}
-
-int needle_matcher_contained_in(needle_matcher *m, int *r) {
-    if (!m || !r) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    return one_row(m, OP_CONTAINED_IN, 0, r, nullptr, nullptr);
-}
-
-// find(FROM, TO): DFAClassBuilder.createFindMethodInternal :625-659.  TO is ignored by the generated
-// indexForwards (its slot is overwritten with this.length, DFAMethodComponents.java:19-21).
-int needle_matcher_find_range(needle_matcher *m, int from, int to, int *r) {
-    (void)to;
-    if (!m || !r) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    *r = 0;
-    if (m->next_start == -1) return NEEDLE_OK; // :629-630
-    const int length = (int)m->s.size();
-    const RefDfa &fw = m->p->t.dfa[W_FORWARDS];
-    int index;
-    int st = 0;
-    bool have_start = false;
-    if (from < 0) return fail(NEEDLE_ERR_INVALID, "from < 0 (StringIndexOutOfBoundsException in the reference)");
-    if (from >= length) {
-        // both generated loops are skipped: indexForwards returns its initial lastMatch (:355-356,468)
-        index = fw.accepting[0] ? 0 : -1;
-    } else {
-        int matched = 0, s32 = -1, e32 = -1;
-        int rc = one_row(m, OP_FIND, from, &matched, &s32, &e32);
-        if (rc) return rc;
-        if (matched) {
-            index = e32 + from;
-            st = s32 + from; // the backward walk is bounded by FROM (:651-652) == index 0 of the sub-row
-            have_start = true;
-        } else {
-            index = -1;
-        }
-    }
-    m->end = index;
-    m->next_start = index;
-    if (index == -1) return NEEDLE_OK;
-    if (!have_start) {
-        // index came from the literal 0 above; start as the reference computes it with an empty walk
-        if (m->p->t.fixed_len >= 0) st = index - m->p->t.fixed_len;
-        else st = m->p->t.dfa[W_BACKWARDS].accepting[0] ? from : 0x7FFFFFFF; // :543-547 with index-1 < FROM
-    }
-    m->start = st;
-    *r = 1;
-    return NEEDLE_OK;
-}
-
-int needle_matcher_find(needle_matcher *m, int *r) {
-    if (!m) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    return needle_matcher_find_range(m, m->next_start, (int)m->s.size(), r); // :616-623
-}
-
-int needle_matcher_start(const needle_matcher *m) { return m ? m->start : -1; }
-int needle_matcher_end(const needle_matcher *m) { return m ? m->end : -1; }
 
 } // extern "C"
 
@@ -3027,7 +2262,7 @@ static const SetPlan *set_plan(const needle_pattern_set *s, int op, int char_wid
     return &s->plan[op][char_width - 1];
 }
 // NEEDLE_ERR_UNSUPPORTED where the set has no plan for this op and char width (arguments as set_plan accepts them).
-static int set_plan_usable(const needle_pattern_set *s, int op, int char_width) {
+int needle::set_plan_usable(const needle_pattern_set *s, int op, int char_width) {
     const std::string &why = s->refused[op][char_width - 1];
     return why.empty() ? NEEDLE_OK : fail(NEEDLE_ERR_UNSUPPORTED, why);
 }
@@ -3059,20 +2294,14 @@ static int set_program(needle_pattern_set *s, int op, int cw, int group, const u
     return NEEDLE_OK;
 }
 
-static int check_set_packed(const needle_pattern_set *s, const needle_packed_view *v, const uint32_t *masks, bool device) {
-    if (!s) return fail(NEEDLE_ERR_INVALID, "pattern set is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (!masks) return fail(NEEDLE_ERR_INVALID, "masks is NULL");
-    if (device && ((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
-    return NEEDLE_OK;
-}
-
 // One launch per group on the caller's stream: group 0 stores the masks, later groups read-modify-write them.
 static int run_set_packed_dev(const needle_pattern_set *cs, int op, const needle_packed_view *v, uint32_t *d_masks, void *stream_) {
     needle_pattern_set *s = const_cast<needle_pattern_set *>(cs);
-    int rc = check_set_packed(s, v, d_masks, true);
+    if (!s) return fail(NEEDLE_ERR_INVALID, "pattern set is NULL");
+    int rc = check_packed(v);
     if (rc) return rc;
+    if (!d_masks) return fail(NEEDLE_ERR_INVALID, "masks is NULL");
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
     if (v->n_rows == 0) return NEEDLE_OK;
     const int cw = (int)v->char_width;
     if ((rc = set_plan_usable(s, op, cw))) return rc;
@@ -3094,42 +2323,6 @@ static int run_set_packed_dev(const needle_pattern_set *cs, int op, const needle
         a.group_mask = (grp.count >= 32 ? 0xFFFFFFFFu : ((1u << grp.count) - 1u)) << grp.first;
         a.store = g == 0 ? 1u : 0u;
         HIP_TRY(launch_packed_set(op, cw, a, n_cus, (hipStream_t)stream_));
-    }
-    return NEEDLE_OK;
-}
-
-// A packed HOST batch: consecutive-row chunks of at most NEEDLE_HOST_CHUNK_BYTES of text are uploaded (offsets rebased to the chunk),
-// scanned where they lie by the _dev entry and their masks downloaded -- the chunking and upload of needle_find_packed16_packed_host.
-static int run_set_packed_host(const needle_pattern_set *s, int op, const needle_packed_view *v, uint32_t *masks) {
-    int rc = check_set_packed(s, v, masks, false);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if ((rc = set_plan_usable(s, op, (int)v->char_width))) return rc;
-    const uint64_t n = v->n_rows, cw = v->char_width;
-    uint64_t max_len = 0;
-    if ((rc = check_packed_host_offsets(v, &max_len))) return rc;
-    if (v->offsets[n] > v->offsets[0] && !v->data) return fail(NEEDLE_ERR_INVALID, "data is NULL");
-    auto up16 = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
-    const std::vector<std::pair<uint64_t, uint64_t>> chunks = packed_host_chunks(v, 8 + 4, 1); // (offset + mask per row)
-    uint64_t biggest = 0, max_rows = 0;
-    for (const auto &c : chunks) {
-        biggest = std::max<uint64_t>(biggest, up16(std::max<uint64_t>((v->offsets[c.second] - v->offsets[c.first]) * cw, 4)));
-        max_rows = std::max<uint64_t>(max_rows, c.second - c.first);
-    }
-    // data | offsets | masks (one buffer for every chunk)
-    const uint64_t o_off = biggest, o_res = o_off + up16((max_rows + 1) * 8), all = o_res + up16(max_rows * 4);
-    DevAllocs dev;
-    uint8_t *d = nullptr;
-    HIP_TRY(dev.alloc(&d, all));
-    std::vector<uint64_t> local;
-    for (const auto &c : chunks) {
-        const uint64_t r0 = c.first, nr = c.second - c.first;
-        needle_packed_view dv;
-        hipError_t e = upload_packed_chunk(v, r0, c.second, d, (uint64_t *)(d + o_off), local, &dv);
-        if (e != hipSuccess) return hip_fail(e, "set_packed_host upload");
-        if ((rc = run_set_packed_dev(s, op, &dv, (uint32_t *)(d + o_res), nullptr))) return rc;
-        e = hipMemcpy(masks + r0, d + o_res, nr * 4, hipMemcpyDeviceToHost); // (synchronises with the scan)
-        if (e != hipSuccess) return hip_fail(e, "set_packed_host download");
     }
     return NEEDLE_OK;
 }
@@ -3210,12 +2403,6 @@ int needle_set_matches_packed_dev(const needle_pattern_set *s, const needle_pack
 }
 int needle_set_contained_in_packed_dev(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *d_masks, void *stream) {
     return run_set_packed_dev(s, OP_CONTAINED_IN, v, d_masks, stream);
-}
-int needle_set_matches_packed_host(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *masks) {
-    return run_set_packed_host(s, OP_MATCHES, v, masks);
-}
-int needle_set_contained_in_packed_host(const needle_pattern_set *s, const needle_packed_view *v, uint32_t *masks) {
-    return run_set_packed_host(s, OP_CONTAINED_IN, v, masks);
 }
 
 } // extern "C"

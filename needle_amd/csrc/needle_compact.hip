@@ -13,18 +13,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-#include <cstdlib>
 #include <functional>
 #include <string>
 
 #include "../../include/needle_hip.h"
+#include "needle_internal.h"
 #include "needle_launch.h"
-
-namespace needle {
-int set_error(int code, const std::string &msg);
-hipError_t scratch_malloc(void **out, size_t bytes, hipStream_t stream); // needle_api.cpp: the library's own memory pool
-hipError_t scratch_free(void *p, hipStream_t stream);
-}
 
 namespace {
 
@@ -114,9 +108,11 @@ __global__ __launch_bounds__(256) void fill_kernel(const uint64_t *bitmap, uint6
 
 int fail(int code, const std::string &msg) { return needle::set_error(code, msg); }
 
+} // namespace
+
 // row_base: added to the row numbers written (chunks of a host batch)
-int find_compact(const needle_pattern *p, const needle_batch_view *v, uint64_t *d_bitmap, needle_match_rec *d_recs, uint64_t cap,
-                 uint64_t *d_n_matched, uint64_t row_base, void *stream_) {
+int needle::find_compact(const needle_pattern *p, const needle_batch_view *v, uint64_t *d_bitmap, needle_match_rec *d_recs, uint64_t cap,
+                         uint64_t *d_n_matched, uint64_t row_base, void *stream_) {
     if (!p || !v) return fail(NEEDLE_ERR_INVALID, "NULL argument");
     if (!d_bitmap || !d_n_matched || (cap && !d_recs)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
     // (per-row lengths are device memory: the stride bounds them, and it may be the limit rounded up to the 16-byte row alignment)
@@ -152,6 +148,8 @@ int find_compact(const needle_pattern *p, const needle_batch_view *v, uint64_t *
     if (e != hipSuccess) return done(fail(NEEDLE_ERR_DEVICE, std::string("compact find kernels: ") + hipGetErrorString(e)));
     return done(NEEDLE_OK);
 }
+
+namespace {
 
 // ---- every match of every row in COMPACT (CSR) form in one call (needle_find_all_compact16_dev).  The two-pass form
 // (needle_count_matches_dev, the caller's prefix sum, needle_find_all_csr_dev) walks the text TWICE; here the text is walked once --
@@ -274,59 +272,6 @@ int find_all_compact16(const needle_pattern *p, const needle_batch_view *v, uint
     });
 }
 
-// ---- host batches: chunks of at most ~2 GiB of rows resident at a time (64-row boundaries: whole bitmap words)
-struct HostChunk {
-    uint8_t *d_rows = nullptr;
-    uint32_t *d_len = nullptr;
-    needle_batch_view view;
-    ~HostChunk() {
-        if (d_rows) (void)hipFree(d_rows);
-        if (d_len) (void)hipFree(d_len);
-    }
-    int upload(const needle_batch_view *v, uint64_t r0, uint64_t cnt) {
-        const uint64_t cw = v->char_width, src_stride = v->row_stride * cw;
-        uint64_t dst_stride = (src_stride + 15) & ~(uint64_t)15;
-        if (dst_stride == 0) dst_stride = 16;
-        hipError_t e = hipMalloc((void **)&d_rows, cnt * dst_stride);
-        const uint8_t *src = (const uint8_t *)v->rows + r0 * src_stride;
-        if (e == hipSuccess) {
-            if (dst_stride == src_stride) e = hipMemcpy(d_rows, src, cnt * src_stride, hipMemcpyHostToDevice);
-            else {
-                e = hipMemset(d_rows, 0, cnt * dst_stride);
-                if (e == hipSuccess && src_stride) e = hipMemcpy2D(d_rows, dst_stride, src, src_stride, src_stride, cnt, hipMemcpyHostToDevice);
-            }
-        }
-        if (e == hipSuccess && v->lengths) {
-            e = hipMalloc((void **)&d_len, cnt * 4);
-            if (e == hipSuccess) e = hipMemcpy(d_len, v->lengths + r0, cnt * 4, hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) return fail(NEEDLE_ERR_DEVICE, std::string("host chunk upload: ") + hipGetErrorString(e));
-        view = *v;
-        view.rows = d_rows;
-        view.lengths = d_len;
-        view.n_rows = cnt;
-        view.row_stride = dst_stride / cw;
-        return NEEDLE_OK;
-    }
-};
-
-int check_host_view(const needle_batch_view *v) {
-    if (!v) return fail(NEEDLE_ERR_INVALID, "batch view is NULL");
-    if (v->char_width != 1 && v->char_width != 2) return fail(NEEDLE_ERR_INVALID, "char_width must be 1 or 2");
-    if (v->n_rows && !v->rows) return fail(NEEDLE_ERR_INVALID, "rows is NULL");
-    if (v->row_len > v->row_stride) return fail(NEEDLE_ERR_INVALID, "row_len > row_stride");
-    if (v->lengths)
-        for (uint64_t r = 0; r < v->n_rows; ++r)
-            if (v->lengths[r] > v->row_stride) return fail(NEEDLE_ERR_INVALID, "lengths[r] > row_stride");
-    return NEEDLE_OK;
-}
-
-uint64_t rows_per_chunk(const needle_batch_view *v) {
-    static const uint64_t kHostChunkBytes = getenv("NEEDLE_HOST_CHUNK_BYTES") ? (uint64_t)atoll(getenv("NEEDLE_HOST_CHUNK_BYTES")) : (2ull << 30);
-    const uint64_t row_bytes = std::max<uint64_t>(16, (v->row_stride * v->char_width + 15) & ~(uint64_t)15);
-    return std::max<uint64_t>(64, (kHostChunkBytes / row_bytes) & ~(uint64_t)63);
-}
-
 } // namespace
 
 namespace needle {
@@ -346,107 +291,7 @@ int needle_find_all_compact16_dev(const needle_pattern *p, const needle_batch_vi
 
 int needle_find_compact_dev(const needle_pattern *p, const needle_batch_view *v, uint64_t *d_bitmap, needle_match_rec *d_recs, uint64_t cap,
                             uint64_t *d_n_matched, void *stream_) {
-    return find_compact(p, v, d_bitmap, d_recs, cap, d_n_matched, 0, stream_);
-}
-
-// Host batch -> bitmap + the matched rows' records: what crosses PCIe on the way back is 1 bit per row + 8 bytes per
-// MATCHED row (needle_find_host: 8 bytes per row).  *n_matched is the total; at most cap records are written.
-int needle_find_compact_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bitmap, needle_match_rec *recs, uint64_t cap,
-                             uint64_t *n_matched) {
-    if (!p || !n_matched) return fail(NEEDLE_ERR_INVALID, "NULL argument");
-    int rc = check_host_view(v);
-    if (rc) return rc;
-    *n_matched = 0;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap || (cap && !recs)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    if ((v->lengths ? v->row_stride : v->row_len) > 65534u) // the caller's own stride: the upload pads it to 16 bytes
-        return fail(NEEDLE_ERR_UNSUPPORTED, "the compact records hold 16-bit offsets: rows of at most 65 534 chars (use needle_find_host)");
-    const uint64_t per = rows_per_chunk(v);
-    for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
-        const uint64_t cnt = std::min<uint64_t>(per, v->n_rows - r0), words = (cnt + 63) / 64;
-        HostChunk ch;
-        if ((rc = ch.upload(v, r0, cnt))) return rc;
-        uint8_t *d_out = nullptr; // bitmap | count | records
-        const uint64_t o_n = (words * 8 + 15) & ~(uint64_t)15, o_rec = o_n + 16;
-        const uint64_t room = cap > *n_matched ? std::min<uint64_t>(cap - *n_matched, cnt) : 0;
-        if (hipMalloc((void **)&d_out, o_rec + room * sizeof(needle_match_rec)) != hipSuccess) return fail(NEEDLE_ERR_DEVICE, "hipMalloc (compact find results)");
-        rc = find_compact(p, &ch.view, (uint64_t *)d_out, (needle_match_rec *)(d_out + o_rec), room, (uint64_t *)(d_out + o_n), r0, nullptr);
-        uint64_t m = 0;
-        hipError_t e = hipSuccess;
-        if (rc == NEEDLE_OK) {
-            e = hipMemcpy(&m, d_out + o_n, 8, hipMemcpyDeviceToHost); // (synchronises with the kernels on the null stream)
-            if (e == hipSuccess) e = hipMemcpy(bitmap + r0 / 64, d_out, words * 8, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && std::min(m, room)) e = hipMemcpy(recs + *n_matched, d_out + o_rec, std::min(m, room) * sizeof(needle_match_rec), hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_out);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(NEEDLE_ERR_DEVICE, std::string("compact find download: ") + hipGetErrorString(e));
-        *n_matched += m;
-    }
-    return NEEDLE_OK;
-}
-
-// needle_find_host with start / end as ONE dword per row (low half start, high half end, 0xFFFF = no match: the form
-// needle_pack_start_end16_dev writes): 4 bytes per row over PCIe instead of 8.  Rows of at most 65 534 chars.
-int needle_find_packed16_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bitmap, uint32_t *start_end16) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_host_view(v);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap || !start_end16) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    if ((v->lengths ? v->row_stride : v->row_len) > 65534u) // the caller's own stride: the upload pads it to 16 bytes
-        return fail(NEEDLE_ERR_UNSUPPORTED, "16-bit offsets: rows of at most 65 534 chars (use needle_find_host)");
-    const uint64_t per = rows_per_chunk(v);
-    for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
-        const uint64_t cnt = std::min<uint64_t>(per, v->n_rows - r0), words = (cnt + 63) / 64;
-        HostChunk ch;
-        if ((rc = ch.upload(v, r0, cnt))) return rc;
-        uint8_t *d_out = nullptr; // bitmap | packed
-        const uint64_t o_p = (words * 8 + 15) & ~(uint64_t)15;
-        if (hipMalloc((void **)&d_out, o_p + cnt * 4) != hipSuccess) return fail(NEEDLE_ERR_DEVICE, "hipMalloc (find results)");
-        rc = needle_find_packed16_dev(p, &ch.view, (uint64_t *)d_out, (uint32_t *)(d_out + o_p), nullptr);
-        hipError_t e = hipSuccess;
-        if (rc == NEEDLE_OK) {
-            e = hipMemcpy(bitmap + r0 / 64, d_out, words * 8, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(start_end16 + r0, d_out + o_p, cnt * 4, hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_out);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(NEEDLE_ERR_DEVICE, std::string("find download: ") + hipGetErrorString(e));
-    }
-    return NEEDLE_OK;
-}
-
-// needle_find_host with start / end as ONE uint16 per row -- start | (end - start) << 8, 0xFFFF = no match, 0xFFFE = the match
-// (0, 256): pack8 of needle_device.h, stored by the scan kernel itself; NEEDLE_UNPACK8_START / _END decode it -- 2 bytes per row over
-// PCIe instead of 8.  Rows of at most 256 chars.
-int needle_find_packed8_host(const needle_pattern *p, const needle_batch_view *v, uint64_t *bitmap, uint16_t *start_len8) {
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_host_view(v);
-    if (rc) return rc;
-    if (v->n_rows == 0) return NEEDLE_OK;
-    if (!bitmap || !start_len8) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    if ((v->lengths ? v->row_stride : v->row_len) > 256u) // the caller's own stride: the upload pads it to 16 bytes
-        return fail(NEEDLE_ERR_UNSUPPORTED, "8-bit start / length: rows of at most 256 chars (use needle_find_packed16_host)");
-    const uint64_t per = rows_per_chunk(v);
-    for (uint64_t r0 = 0; r0 < v->n_rows; r0 += per) {
-        const uint64_t cnt = std::min<uint64_t>(per, v->n_rows - r0), words = (cnt + 63) / 64;
-        HostChunk ch;
-        if ((rc = ch.upload(v, r0, cnt))) return rc;
-        uint8_t *d_out = nullptr; // bitmap | packed
-        const uint64_t o_p = (words * 8 + 15) & ~(uint64_t)15;
-        if (hipMalloc((void **)&d_out, o_p + cnt * 2) != hipSuccess) return fail(NEEDLE_ERR_DEVICE, "hipMalloc (find results)");
-        rc = needle_find_packed8_dev(p, &ch.view, (uint64_t *)d_out, (uint16_t *)(d_out + o_p), nullptr);
-        hipError_t e = hipSuccess;
-        if (rc == NEEDLE_OK) {
-            e = hipMemcpy(bitmap + r0 / 64, d_out, words * 8, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(start_len8 + r0, d_out + o_p, cnt * 2, hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_out);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(NEEDLE_ERR_DEVICE, std::string("find download: ") + hipGetErrorString(e));
-    }
-    return NEEDLE_OK;
+    return needle::find_compact(p, v, d_bitmap, d_recs, cap, d_n_matched, 0, stream_);
 }
 
 } // extern "C"

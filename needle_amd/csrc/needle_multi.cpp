@@ -16,10 +16,7 @@
 #include <vector>
 
 #include "../../include/needle_hip.h"
-
-namespace needle {
-int set_error(int code, const std::string &msg); // needle_api.cpp: the calling thread's needle_last_error()
-}
+#include "needle_internal.h"
 
 namespace {
 

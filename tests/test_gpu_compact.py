@@ -80,6 +80,11 @@ hw, hrec = p.find_compact(host)      # NEEDLE_HOST_CHUNK_BYTES = 1 MiB: 8192-row
 _check_records(hrec, len(hrec), hw, m, s, e)
 pw, se = p.find_packed16_host(host)
 assert (pw == hw).all() and ((se & 0xFFFF).astype(np.int64)[m] == s[m]).all() and ((se >> 16).astype(np.int64)[m] == e[m]).all() and (se[~m] == 0xFFFFFFFF).all()
+fw, fs, fe = p.find_batch(host)      # the int32 form, and needle_find_packed8_host (rows of 128 chars: start | length << 8) against it
+w8, sl = p.find_packed8_host(host)
+ln = (fe - fs).astype(np.int64)
+assert (w8 == fw).all() and (fw == hw).all() and (fs[m] == s[m]).all() and (fe[m] == e[m]).all()
+assert (sl[m] == np.where(ln > 255, 0xFFFE, (fs & 0xFF) | (ln << 8))[m]).all() and (sl[~m] == 0xFFFF).all()
 print("CHUNKED-OK")
 '''
 

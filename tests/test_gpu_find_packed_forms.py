@@ -244,11 +244,26 @@ sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import numpy as np, torch
 import test_gpu_find_packed_forms as T
 from test_gpu_configs import compiled
-from test_gpu_packed_dev import layout_rows
+from test_gpu_packed_dev import device_packed, layout_rows
 p, o = compiled("[0-9]+")
 rows = layout_rows(np.random.default_rng(3), [ord(ch) for ch in "abc 0123"], [], n=3000, max_len=200)
 T.check_forms(p, rows, np.uint8, lead=17, trail=3, junk=[ord("5")], what="chunked host")
 T.check_forms(p, [r.astype(np.uint16) for r in rows], np.uint16, lead=2, trail=0, junk=[ord("5")], what="chunked host 16")
+# needle_{find,contained_in,matches}_packed_host on the same host arrays against the oracle: as the rows stand (one length class, many
+# chunks), and with one 5 000-char row among them (the padded rows exceed 4x the text + 64 KiB: length classes, each of them chunked)
+from needle_amd.pattern import unpack_bitmap
+want = [(o.find(s), o.matches(s)) for s in (r.tobytes().decode("latin-1") for r in rows)]
+long_row = np.random.default_rng(5).choice(np.array([ord(ch) for ch in "abc 0123"], np.uint8), 5000)
+long_want = (o.find(long_row.tobytes().decode("latin-1")), o.matches(long_row.tobytes().decode("latin-1")))
+for rs, wt in ((rows, want), (rows[:1234] + [long_row] + rows[1234:], want[:1234] + [long_want] + want[1234:])):
+    for dtype in (np.uint8, np.uint16):
+        data, offsets = device_packed([r.astype(dtype) for r in rs], dtype, 17, 3, [ord("5")])
+        hd, ho = data.cpu().numpy().view(dtype), offsets.cpu().numpy()
+        fw, fs, fe = p.find_packed(hd, ho)
+        got, cb, mb = (unpack_bitmap(w, len(rs)) for w in (fw, p.contained_in_packed(hd, ho), p.matches_packed(hd, ho)))
+        for i, ((found, st, en), full) in enumerate(wt):
+            assert got[i] == found and cb[i] == found and mb[i] == full, (i, dtype)
+            assert (fs[i], fe[i]) == ((st, en) if found else (-1, -1)), (i, dtype)
 print("HOST-CHUNKED-OK")
 '''
     r = subprocess.run([sys.executable, "-c", child], env=dict(os.environ, NEEDLE_HOST_CHUNK_BYTES="20000"), capture_output=True, text=True,
