@@ -29,6 +29,7 @@ int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uin
                       const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill);
 // needle_find_all.hip, needle_find_all_ls.hip: every match of every row in one pass
 hipError_t launch_find_all(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream);
+bool find_all_lane_shape(uint32_t prog_lds_bytes, int *waves, int *chb); // (the per-lane kernels' one candidate list, packed rows included)
 hipError_t launch_find_all_lockstep(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream);
 bool find_all_lockstep_shape_ok(const FindAllArgs &fa);
 // needle_stripe.hip: few long rows (stripes, speculative stripes), the round-per-match find-all's collect pass, packed -> fixed stride

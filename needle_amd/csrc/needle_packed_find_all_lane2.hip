@@ -7,15 +7,8 @@ hipError_t launch_packed_find_all_lane1(const PackedFindAllArgs &a, int chb, int
 bool packed_find_all_lane_mode(uint32_t mode) { return mode == MODE_PACK || mode == MODE_TABLE8 || mode == MODE_TABLE16; }
 
 bool packed_find_all_lane_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb) {
-    const size_t p = (prog_lds_bytes + 15u) & ~15u, cap = 160u * 1024u;
-    static const int cand[6][2] = {{16, 128}, {12, 128}, {16, 64}, {12, 64}, {8, 64}, {4, 64}}; // (launch_find_all's)
-    (void)char_width;
-    for (const auto &c : cand)
-        if (p + (size_t)c[0] * 64 * c[1] <= cap) {
-            *waves = c[0], *chb = c[1];
-            return true;
-        }
-    return false;
+    (void)char_width; // (no candidate spills for either width)
+    return find_all_lane_shape(prog_lds_bytes, waves, chb);
 }
 
 // One persistent workgroup per CU, as launch_packed_find_all.
