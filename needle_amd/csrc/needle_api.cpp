@@ -1167,22 +1167,35 @@ static int find_all_filter_program(needle_pattern *p, int cw, FilterChoice *c, c
 
 // The "more" flag of a one-pass find-all launch: a zeroed scratch word the kernel sets when some row has a match beyond its last slot.
 // launch(d_more) enqueues the kernel (and what belongs behind it); the flag is read back -- the call's only synchronisation -- only when the
-// caller asked whether its slots sufficed (more != nullptr).
+// caller asked whether its slots sufficed (more != nullptr).  d_more[1] is a second zeroed word for a flag of the launch's own (the packed
+// kernel's "a row is too long"), read back with the first into *second when the caller asked for it.
 template <class Launch>
-static int with_more_flag(hipStream_t stream, int *more, const char *what, Launch &&launch) {
+static int with_more_flag(hipStream_t stream, int *more, const char *what, Launch &&launch, int *second = nullptr) {
     int32_t *d_more = nullptr;
     HIP_TRY(scratch_malloc((void **)&d_more, 16, stream));
-    hipError_t e = hipMemsetAsync(d_more, 0, 4, stream);
+    hipError_t e = hipMemsetAsync(d_more, 0, 8, stream);
     if (e == hipSuccess) e = launch(d_more);
-    int32_t m = 0;
-    if (e == hipSuccess && more) {
-        e = hipMemcpyAsync(&m, d_more, 4, hipMemcpyDeviceToHost, stream);
+    int32_t h[2] = {0, 0};
+    if (e == hipSuccess && (more || second)) {
+        e = hipMemcpyAsync(h, d_more, 8, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
     }
     (void)scratch_free(d_more, stream);
     if (e != hipSuccess) return hip_fail(e, what);
-    if (more) *more = m != 0;
+    if (more) *more = h[0] != 0;
+    if (second) *second = h[1] != 0;
     return NEEDLE_OK;
+}
+
+// The find-all transducer program of a pattern for rows of cw: the lengths transducer, else -- for a pattern without bounded match lengths
+// -- the RUN transducer (`[0-9]+`, `[a-z]{3}[a-z]*`: starts from a per-lane run-start register), or *tp = nullptr.  The order of
+// needle_pattern_find_all_transducer.  lengths_on / runs_on: the caller's switches.
+static int find_all_transducer_program(needle_pattern *p, int cw, bool lengths_on, bool runs_on, const DevProgram **tp, int *n_cus) {
+    *tp = nullptr;
+    int rc = NEEDLE_OK;
+    if (lengths_on && (rc = get_program(p, W_FORWARDS, cw, V_FA_TRANSDUCER, tp, n_cus))) return rc;
+    if (!*tp && runs_on && p->t.fixed_len < 0) rc = get_program(p, W_FORWARDS, cw, V_FA_RUNS, tp, n_cus);
+    return rc;
 }
 
 int needle::check_packed(const needle_packed_view *v) {
@@ -1267,16 +1280,11 @@ static bool packed_find_all_takes(const ProgHeader &h, int char_width) {
     return h.ft_on && packed_find_all_shape(h.lds_bytes, char_width, &waves, &chb);
 }
 
-// The transducer program the packed find-all kernel walks for this pattern and char width (the lengths transducer, else the RUN
-// transducer -- the order of needle_pattern_find_all_transducer), or *tp = nullptr: the pattern goes by conversion.
+// The transducer program the packed find-all kernel walks for this pattern and char width (find_all_transducer_program; the packed
+// entries honour none of the fixed-stride entries' switches), or *tp = nullptr: the pattern goes by conversion.
 static int packed_find_all_program(needle_pattern *p, int cw, const DevProgram **tp, int *n_cus) {
-    *tp = nullptr;
-    int rc = get_program(p, W_FORWARDS, cw, V_FA_TRANSDUCER, tp, n_cus);
+    const int rc = find_all_transducer_program(p, cw, true, true, tp, n_cus);
     if (rc) return rc;
-    if (!*tp && p->t.fixed_len < 0) {
-        rc = get_program(p, W_FORWARDS, cw, V_FA_RUNS, tp, n_cus);
-        if (rc) return rc;
-    }
     if (*tp && !packed_find_all_takes((*tp)->prog.hdr, cw)) *tp = nullptr;
     return NEEDLE_OK;
 }
@@ -1297,22 +1305,11 @@ static int packed_find_all_launch(const needle_packed_view *v, const DevProgram 
     a.f.kshift = d_blocks ? 6u : 0u;
     a.f.count_only = count_only ? 1u : 0u;
     a.row_offsets = v->offsets;
-    int32_t *d_flags = nullptr; // [0] more, [1] too long
-    HIP_TRY(scratch_malloc((void **)&d_flags, 16, stream));
-    a.f.more = d_flags;
-    a.too_long = d_blocks ? d_flags + 1 : nullptr;
-    hipError_t e = hipMemsetAsync(d_flags, 0, 8, stream);
-    if (e == hipSuccess) e = launch_packed_find_all((int)v->char_width, a, n_cus, stream);
-    int32_t h[2] = {0, 0};
-    if (e == hipSuccess && (more || too_long)) { // the only synchronisation: the caller asked whether its slots sufficed
-        e = hipMemcpyAsync(h, d_flags, 8, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    }
-    (void)scratch_free(d_flags, stream);
-    if (e != hipSuccess) return hip_fail(e, "find_all (packed kernel)");
-    if (more) *more = h[0] != 0;
-    if (too_long) *too_long = h[1] != 0;
-    return NEEDLE_OK;
+    return with_more_flag(stream, more, "find_all (packed kernel)", [&](int32_t *d_more) {
+        a.f.more = d_more;
+        a.too_long = d_blocks ? d_more + 1 : nullptr;
+        return launch_packed_find_all((int)v->char_width, a, n_cus, stream);
+    }, too_long);
 }
 
 // The one answer to "does this per-lane find-all program take the packed per-lane kernel on rows of char_width"
@@ -2145,16 +2142,9 @@ static int find_all_one_pass(needle_pattern *p, const needle_batch_view *v, uint
     if (lockstep_on && find_all_lockstep_shape_ok(fa)) {
         const DevProgram *tp = nullptr;
         int cus = 0;
-        if (lengths_on) {
-            rc = get_program(p, W_FORWARDS, cw, V_FA_TRANSDUCER, &tp, &cus);
-            if (rc) return rc;
-        }
-        // ... or, without bounded match lengths, the RUN transducer (`[0-9]+`, `[a-z]{3}[a-z]*`: starts from a per-lane run-start register)
+        // NEEDLE_FIND_ALL_LENGTHS=0 / NEEDLE_FIND_ALL_RUNS=0: without the lengths / the RUN transducer (A/B, tests)
         static const bool runs_on = (getenv("NEEDLE_FIND_ALL_RUNS") ? atoi(getenv("NEEDLE_FIND_ALL_RUNS")) : 1) != 0;
-        if (!tp && runs_on && p->t.fixed_len < 0) {
-            rc = get_program(p, W_FORWARDS, cw, V_FA_RUNS, &tp, &cus);
-            if (rc) return rc;
-        }
+        if ((rc = find_all_transducer_program(p, cw, lengths_on, runs_on, &tp, &cus))) return rc;
         if (tp) {
             fa.s = scan_args(v, stride_bytes, tp, nullptr, -1, ScanOut());
             return with_more_flag(stream, more, "find_all (lock-step kernel)", [&](int32_t *d_more) {

@@ -1,5 +1,6 @@
-// Launch arguments of the one-pass find-all kernels (needle_find_all.hip, needle_find_all_ls.hip, needle_packed_find_all.h); shared
-// with the launchers' caller in needle_api.cpp.
+// Launch arguments of the one-pass find-all kernels (needle_find_all.hip, needle_find_all_ls.hip, needle_packed_find_all.h,
+// needle_packed_find_all_lane.h) and of the walks they share (needle_find_all_walk.h: per-lane; needle_find_all_ls_walk.h: lock-step);
+// shared with the launchers' caller in needle_api.cpp.
 #pragma once
 #include <stddef.h>
 #include "needle_device.h"

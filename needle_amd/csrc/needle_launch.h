@@ -32,6 +32,9 @@ hipError_t launch_find_all(int char_width, const FindAllArgs &fa, int n_cus, hip
 bool find_all_lane_shape(uint32_t prog_lds_bytes, int *waves, int *chb); // (the per-lane kernels' one candidate list, packed rows included)
 hipError_t launch_find_all_lockstep(int char_width, const FindAllArgs &fa, int n_cus, hipStream_t stream);
 bool find_all_lockstep_shape_ok(const FindAllArgs &fa);
+// (the lock-step kernels' one candidate list and launch geometry, packed rows included; tiles128: 128-byte tiles per lane allowed)
+bool find_all_lockstep_shape(uint32_t prog_lds_bytes, bool tiles128, int *waves, int *chb);
+void find_all_lockstep_grid(uint32_t prog_lds_bytes, uint64_t n_rows, int waves, int chb, int n_cus, int *grid, size_t *lds);
 // needle_stripe.hip: few long rows (stripes, speculative stripes), the round-per-match find-all's collect pass, packed -> fixed stride
 hipError_t launch_find_all_collect(uint64_t n_rows, uint32_t slots, uint32_t k, const int32_t *s, const int32_t *e, int32_t *cursor,
                                    uint32_t *counts, int32_t *starts, int32_t *ends, int32_t *any_hit, int n_cus, hipStream_t stream);

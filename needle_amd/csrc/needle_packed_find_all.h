@@ -10,7 +10,10 @@
 //       entry = T[(entry >> 4) * row_bytes + column(char)],   log = {entry, log} >> 4,
 //   the 4-bit match codes filed from the log.  Both transducers: the lengths one (get_program variant 8, a code names (length, k))
 //   and the RUN one (variant 11, bit 0: a match ends in front of this char, bit 1: this char may begin a run, with the per-lane
-//   run_start register).
+//   run_start register).  The walk set-up, the chain, the decode and the row's end below are a COPY of needle_find_all_ls_walk.h's
+//   (the fixed-stride kernel's), kept on purpose: written over that header's lane-state struct and Rows policy this kernel's ISA is
+//   the same up to a handful of instructions, yet three of its four rate figures run 0.4-0.8 % slower, in every round, whichever of the
+//   chain and the decode it keeps to itself (profiles/find_all_packed.md).  A fix to the decode there is a fix to make here too.
 //   Row edges.  A row starts and ends at arbitrary code units.  The transducer programs have no PRE (identity) column, so chars of the
 //   row's first block that lie before its start are SELECTED away on the state chain: the entry stays the start entry (code 0, no run
 //   start).  Chars at or after the row's end take the PAD column: the first one emits what is pending and leads to the dead state, whose
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_find_all_kernel(co
         *(u32x4 *)(smem + i) = *(const u32x4 *)(a.prog + i);
     __syncthreads();
 
-    // walk constants: as find_all_lockstep_kernel sets them up
+    // walk constants: as find_all_ls_setup (needle_find_all_ls_walk.h) sets them up
     Walk wk;
     wk.ncols_e = a.hdr.n_cols * 2u;
     wk.pad_e = a.hdr.pad_col * 2u;
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_find_all_kernel(co
     // a match filed at char index pos with d = codes[code] = (k + length) | k << 16: [pos - (k + length), pos - k) (needle_device.h)
     auto file = [&](bool hit, uint32_t pos, uint32_t d) __attribute__((always_inline)) { put(hit, pos - (d & 0xFFFFu), pos - (d >> 16)); };
 
-    // The match codes of 8 consecutive chars (char j in nibble j of h; pos0 = row index of char 0) -- as find_all_lockstep_kernel's decode
+    // The match codes of 8 consecutive chars (char j in nibble j of h; pos0 = row index of char 0) -- as find_all_ls_decode (needle_find_all_ls_walk.h)
     const bool direct_codes = a.hdr.ft_direct != 0u;
     const bool odd_codes = a.hdr.ft_odd != 0u;
     auto decode = [&](uint32_t h, uint32_t pos0) __attribute__((always_inline)) {
@@ -231,10 +234,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void packed_find_all_kernel(co
     packed_stream<CW, CHB>(lane, wave, n_waves, a.rows, pf.row_offsets, n_rows, win, rs, re, begin_group, walk_window,
                            []() __attribute__((always_inline)) { return true; }, [&]() __attribute__((always_inline)) { return rs; }, finish_rows);
 }
-
-// Waves per workgroup x window bytes per lane for a transducer program of prog_lds_bytes on rows of char_width (the lock-step kernel's
-// candidates: the program plus one window per wave within the 160 KiB of LDS).  false: no shape fits.
-bool packed_find_all_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
 
 template <int CW, int CHB, bool RUNS>
 static hipError_t launch_packed_find_all_one(const PackedFindAllArgs &a, int grid, int waves, size_t lds, hipStream_t stream) {

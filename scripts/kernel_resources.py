@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""VGPRs / scratch of every instantiation of the tiled scan kernel, of the per-lane find-all kernel of fixed-stride rows, of the
-packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel
+"""VGPRs / scratch of every instantiation of the tiled scan kernel, of the per-lane and the lock-step find-all kernels of fixed-stride
+rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel
 and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip)
 (cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
@@ -14,7 +14,7 @@ modes = {"0": "pack", "1": "table8", "2": "table16", "3": "hbm", "4": "pair", "5
 procs = []
 tmp = tempfile.mkdtemp()
 for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", "needle_scan_find2",
-           "needle_find_all",
+           "needle_find_all", "needle_find_all_ls",
            "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2", "needle_packed_next1",
            "needle_packed_next2", "needle_packed_forms1", "needle_packed_forms2",
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
@@ -50,6 +50,12 @@ for k, sc, v in sorted(rows):
     m = re.search(r"\d+find_all_kernelILi(\d)ELi(\d)ELi(\d+)ELb(\d)E", k)  # (the digits: the mangled name's length -- not packed_find_all_kernel)
     if m:
         print("%4d %4d  find-all    cw%s %-8s %-11s tile %3d B" % (sc, v, m.group(1), modes[m.group(2)], "skip-states" if m.group(4) == "1" else "", int(m.group(3))))
+# ... and so is the lock-step find-all kernel of fixed-stride rows
+print("fixed-stride lock-step find-all kernels (needle_find_all_ls.hip): scratch bytes / VGPRs / kernel / tile per lane")
+for k, sc, v in sorted(rows):
+    m = re.search(r"find_all_lockstep_kernelILi(\d)ELb(\d)ELi(\d+)ELb(\d)E", k)
+    if m:
+        print("%4d %4d  find-all    cw%s %-8s %-5s tile %3d B" % (sc, v, m.group(1), "run" if m.group(4) == "1" else "lengths", "guard" if m.group(2) == "1" else "full", int(m.group(3))))
 # the packed-rows kernels are always listed, spilling or not
 print("packed-rows kernels (needle_packed.h): scratch bytes / VGPRs / kernel / LDS window per wave")
 for k, sc, v in sorted(rows):

@@ -90,7 +90,8 @@ assert total > 20000, total
 # adjacent and overlapping candidates, one-length patterns; random text over the pattern's own letters
 rng = np.random.default_rng(3)
 for rx in ["abc|bcd|cdefg|a|xyzzy|zzy", "(foo|foobar|bar|barbaz|baz)x?", "ab|abcd|cdx|dxyz", "Sherlock|Holmes|Watson|Irene|Adler|John|Baker",
-           "abcdef|bcd|cdefgh|f", "Sherlock", "aab|ab|b", "[ab]c|a[bc]d|[abc]{4}", "abcdefgh|abcd", "a.c|ab"]:
+           "abcdef|bcd|cdefgh|f", "Sherlock", "aab|ab|b", "[ab]c|a[bc]d|[abc]{4}", "abcdefgh|abcd", "a.c|ab",
+           "abcdefghijklmno|abc|abcdefg|abcdefghijk"]:  # (13 codes: the codes table without the odd numbering)
     p = DFACompiler.compile(rx, "t", 0)
     o, _ = oracle_for(rx, 0)
     assert p.find_all_transducer(1) is not None, rx

@@ -94,6 +94,76 @@ def test_patterns_and_layouts(regex, cw, alphabet, plants, junk, kernel):
     check_all(p, o, [np.zeros(0, dtype)] * 70, dtype, lead=9, trail=9, junk=jk, what="only empty rows")
 
 
+def decode_form(ft):
+    """Which of the lock-step decode's five forms (needle_find_all_ls_walk.h find_all_ls_decode) a transducer program takes, read off its
+    codes table as the lowering numbers it (needle_lower.cpp): codes[c] = (k + length) | k << 16, codes[0] = 0."""
+    if ft["kind"] == 2:
+        return "run", 0
+    codes = ft["blob"][ft["codes_off"]:ft["codes_off"] + 64].view(np.uint32)
+    assert codes[0] == 0
+    used = [(c, int(d >> 16), int(d & 0xFFFF) - int(d >> 16)) for c, d in enumerate(codes) if d]  # (code, k, length)
+    if all(k == 0 and 1 <= length <= 7 for _, k, length in used):
+        assert all(c == 2 * length + 1 for c, _, length in used)
+        return "direct 2", len(used)
+    if all(k == 0 and 1 <= length <= 15 for _, k, length in used):
+        assert all(c == length for c, _, length in used)
+        return "direct 1", len(used)
+    assert any(k > 0 for _, k, _ in used)          # (what keeps these patterns off the direct forms)
+    if len(used) <= 8:
+        assert all(c % 2 == 1 for c, _, _ in used)
+        return "table, odd codes", len(used)
+    return "table", len(used)
+
+
+DECODE_FORMS = [
+    # (regex, char widths, form, codes, a match, adjacent matches: several ends within 8 chars)
+    ("[0-9]+", (1, 2), "run", 0, "0123", "1 22 3 4 55 6 7 "),
+    ("[α-ω]{2}[α-ω]*", (2,), "run", 0, "αβγ", "αβ γω αβ ωω αβγ "),
+    ("Sherlock|Holmes|Watson|Irene|Adler|John|Baker", (1, 2), "direct 1", None, "Sherlock", "JohnJohnJohnIrene"),
+    ("a.c|ab", (1, 2), "direct 2", None, "axc", "ababababab"),
+    ("abcdefgh|abcd", (1, 2), "table, odd codes", 5, "abcdefgh", "abcdabcdabcdabcd"),
+    ("abcdefghijklmno|abc|abcdefg|abcdefghijk", (1, 2), "table", 13, "abcdefghijklmno", "abcabcabcabcabc"),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regex,cw,form,n_codes,word,dense", [(rx, cw, f, nc, w, d) for rx, cws, f, nc, w, d in DECODE_FORMS for cw in cws])
+def test_every_decode_form_in_both_layouts(regex, cw, form, n_codes, word, dense):
+    """The five forms of the lock-step decode, each on packed rows and (check_all) on the same rows at a fixed stride: a lowering change
+    that moves a pattern to another form fails here instead of dropping the form's coverage."""
+    p, o = compiled(regex)
+    dtype = np.uint8 if cw == 1 else np.uint16
+    got_form, got_codes = decode_form(p.find_all_transducer(cw))
+    assert got_form == form and (n_codes is None or got_codes == n_codes), (got_form, got_codes)
+    rng = np.random.default_rng(len(regex) + cw)
+    arr = lambda s: np.array([ord(ch) for ch in s], dtype)
+    letters = arr("".join(sorted(set(ch for ch in regex + word + dense if ch.isalnum()))) + " ")
+    pieces = [arr(word), arr(word[:-1]), arr(dense), arr(" ")]
+    def row(n):
+        parts, have = [], 0
+        while have < n:
+            parts.append(pieces[int(rng.integers(0, 4))] if rng.random() < 0.6 else rng.choice(letters, int(rng.integers(1, 9))))
+            have += parts[-1].size
+        return np.concatenate(parts)[:n].astype(dtype) if parts else np.zeros(0, dtype)
+    rows = [row(int(n)) for n in rng.integers(0, 301, 130)]
+    rows[0] = np.zeros(0, dtype)
+    rows[1] = arr("  " + word)                               # ends with a match's last char: emitted by the PAD transition
+    rows[2] = arr("  " + word[:-1])                          # cut one char short
+    rows[3] = arr(dense * 3)
+    rows[129] = row(300)
+    per16 = 16 // cw                                         # 16 rows of 33 chars: their ends take every position in a 16-byte block,
+    for i in range(64, 80):                                  # so one ends on a block boundary of the buffer whatever the lead is
+        rows[i] = arr(" " * (33 - len(word)) + word)
+    ends = np.cumsum([len(r) for r in rows])[64:80]
+    assert len(set((ends % per16).tolist())) == per16
+    for lead in (5, 0):             # (check_all compares every GPU result with the oracle; it returns the ORACLE's matches)
+        off, st, en = check_all(p, o, rows, dtype, lead=lead, trail=7, junk=arr(word).tolist(), kernel=True, what="lead %d" % lead)
+    # not result checks: the input holds what it was built to hold, by the oracle's matches (the same for either lead)
+    assert off[2] - off[1] >= 1 and en[off[2] - 1] == len(rows[1])      # a match that ends with its row
+    assert off[4] - off[3] >= 6                                         # adjacent matches
+    assert (np.diff(off)[64:80] >= 1).all() and (en[off[65:81] - 1] == 33).all()
+
+
 @pytest.mark.gpu
 def test_c5_script_runs_utf16():
     from needle_amd import workload as W
