@@ -340,6 +340,36 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         return new Matches(matchOffsets, start, end);
     }
 
+    /**
+     * Every non-overlapping match of every haystack -- the matches {@link #findAllStrings} reports -- replaced by the literal
+     * {@code replacement}: what a caller gets who loops the reference's {@code matcher.find()} and appends to a StringBuilder (an
+     * empty match is replaced once and ends its haystack).  The replacement is literal ({@code $1} and {@code \} mean themselves: the
+     * reference has no groups) and holds at most 4096 chars; an empty one deletes the matches.  This is not
+     * {@code java.util.regex}'s replaceAll for patterns that match the empty string, which enumerates empty matches differently.
+     * The strings are flattened as in {@link #findBatch}: a sizing call, then the call that files the text
+     * (needle_replace_all_packed_host).
+     */
+    public String[] replaceAllStrings(String[] haystacks, String replacement) {
+        long[] offsets = new long[haystacks.length + 1];
+        char[] data = flatten(haystacks, offsets);
+        char[] repl = replacement.toCharArray();
+        long[] outOffsets = new long[haystacks.length + 1];
+        long[] total = new long[1];
+        check(Native.replaceAllPackedHost(handle, data, offsets, repl, outOffsets, null, total), null);
+        if (total[0] > Integer.MAX_VALUE - 8) {
+            throw new IllegalArgumentException("the result does not fit a char[]: " + total[0] + " chars");
+        }
+        char[] out = new char[(int) total[0]];
+        if (total[0] > 0) {
+            check(Native.replaceAllPackedHost(handle, data, offsets, repl, outOffsets, out, total), null);
+        }
+        String[] result = new String[haystacks.length];
+        for (int i = 0; i < haystacks.length; i++) {
+            result[i] = new String(out, (int) outOffsets[i], (int) (outOffsets[i + 1] - outOffsets[i]));
+        }
+        return result;
+    }
+
     /** The native pattern (GpuPatternSet copies its tables at creation). */
     long handle() {
         return handle;

@@ -58,6 +58,13 @@ final class Native {
     static native int findAllPackedHost(long handle, char[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end, long[] total);
 
     /**
+     * needle_replace_all_packed_host: every non-overlapping match of every packed haystack (data + offsets as packedHost) replaced by the
+     * literal replacement (UTF-16 code units, at most 4096; empty: the matches are deleted).  outOffsets long[n + 1] and total long[1]
+     * are always filled; out char[capacity] (null: size only) holds the result text when total[0] <= capacity.
+     */
+    static native int replaceAllPackedHost(long handle, char[] data, long[] offsets, char[] replacement, long[] outOffsets, char[] out, long[] total);
+
+    /**
      * needle_find_packed16_packed_host / needle_find_packed8_packed_host: find() of every packed haystack with a row's result as
      * one int (start | end << 16; haystacks of at most 65 534 chars) or one short (start | (end - start) << 8, 0xFFFF no match,
      * 0xFFFE the match (0, 256); haystacks of at most 256 chars).  Longer haystacks: NEEDLE_ERR_UNSUPPORTED.

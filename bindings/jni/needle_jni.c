@@ -357,6 +357,38 @@ NATIVE(jint, findAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data,
     return rc;
 }
 
+/* needle_replace_all_packed_host: data + offsets as packedHost; replacement char[] (may be empty, not null); outOffsets long[n + 1];
+ * out char[capacity] (may be null: size only); total long[1]. */
+NATIVE(jint, replaceAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data, jlongArray offsets, jcharArray replacement, jlongArray outOffsets, jcharArray out, jlongArray total) {
+    if (!data || !offsets || !replacement || !outOffsets || !total) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, outOffsets) < n1 || (*env)->GetArrayLength(env, total) < 1) return NEEDLE_ERR_INVALID;
+    const jsize cap = out ? (*env)->GetArrayLength(env, out) : 0;
+    const jsize rn = (*env)->GetArrayLength(env, replacement);
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jchar *r = (*env)->GetCharArrayElements(env, replacement, NULL);
+    jlong *oo = (*env)->GetLongArrayElements(env, outOffsets, NULL);
+    jchar *text = cap ? (*env)->GetCharArrayElements(env, out, NULL) : NULL;
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    uint64_t t = 0;
+    int rc = needle_replace_all_packed_host((const needle_pattern *)(intptr_t)h, &v, rn ? (const void *)r : NULL, (uint32_t)rn, (uint64_t *)oo, text,
+                                            (uint64_t)cap, &t);
+    jlong jt = (jlong)t;
+    (*env)->SetLongArrayRegion(env, total, 0, 1, &jt);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseCharArrayElements(env, replacement, r, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, outOffsets, oo, 0);
+    if (text) (*env)->ReleaseCharArrayElements(env, out, text, 0);
+    return rc;
+}
+
 /* needle_find_packed16_packed_host / needle_find_packed8_packed_host: data + offsets as packedHost; bitmap long[(n + 63) / 64];
  * the results int[n] (16) or short[n] (8). */
 static jint find_packed_compact_host(JNIEnv *env, jlong h, jcharArray data, jlongArray offsets, jlongArray bitmap, jarray out, int bits) {

@@ -1488,6 +1488,68 @@ int needle_find_all_csr_packed_dev(const needle_pattern *cp, const needle_packed
     return packed_find_all_route(p, v, nullptr, d_offsets, d_start, d_end, false, more, (hipStream_t)stream_);
 }
 
+// The splice (needle_replace.hip): pure functions of (text, match list, replacement) -- no pattern, no route.  The checks of the packed
+// device entries, then the kernels' arguments; n_rows == 0 has returned before this is called.
+static int replace_args(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start, const int32_t *d_end, uint32_t repl_len,
+                        ReplaceArgs *a) {
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    if (!d_match_offsets) return fail(NEEDLE_ERR_INVALID, "match offsets is NULL");
+    if (repl_len > NEEDLE_REPLACE_MAX_UNITS) return fail(NEEDLE_ERR_INVALID, "replacement longer than NEEDLE_REPLACE_MAX_UNITS code units");
+    memset(a, 0, sizeof(*a));
+    a->data = (const uint8_t *)v->data;
+    a->in_off = v->offsets;
+    a->n_rows = v->n_rows;
+    a->cw = v->char_width;
+    a->repl_len = repl_len;
+    a->match_off = d_match_offsets;
+    a->start = d_start;
+    a->end = d_end;
+    return NEEDLE_OK;
+}
+
+int needle_replace_all_lengths_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start,
+                                          const int32_t *d_end, uint32_t repl_len, uint64_t *d_out_lengths, void *stream_) {
+    ReplaceArgs a;
+    int rc = replace_args(v, d_match_offsets, d_start, d_end, repl_len, &a);
+    if (rc) return rc;
+    if (!d_out_lengths) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    a.out_len = d_out_lengths;
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(launch_replace_lengths(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+int needle_replace_all_fill_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start,
+                                       const int32_t *d_end, const void *repl, uint32_t repl_len, const uint64_t *d_out_offsets,
+                                       void *d_out_data, void *stream_) {
+    ReplaceArgs a;
+    int rc = replace_args(v, d_match_offsets, d_start, d_end, repl_len, &a);
+    if (rc) return rc;
+    if (!d_out_offsets || !d_out_data) return fail(NEEDLE_ERR_INVALID, "output offsets / buffer is NULL");
+    if (((uintptr_t)d_out_data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "output data must be 4-byte aligned");
+    if (repl_len && !repl) return fail(NEEDLE_ERR_INVALID, "replacement is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    a.out_off = d_out_offsets;
+    a.out = (uint8_t *)d_out_data;
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const uint32_t bytes = repl_len * v->char_width;
+    uint8_t *d_repl = nullptr; // (whole 16 bytes: the kernel stages it with 16-byte loads)
+    if (bytes) HIP_TRY(scratch_malloc((void **)&d_repl, (bytes + 15u) & ~15u, stream));
+    hipError_t e = bytes ? launch_replace_put(repl, bytes, d_repl, stream) : hipSuccess;
+    a.repl = d_repl;
+    if (e == hipSuccess) e = launch_replace_fill(a, cus, stream);
+    if (d_repl) (void)scratch_free(d_repl, stream);
+    return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_all_fill_packed_dev");
+}
+
 int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t max_per_row, uint64_t *d_offsets,
                                          uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);

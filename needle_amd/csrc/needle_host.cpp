@@ -671,6 +671,96 @@ int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed
     return rc;
 }
 
+// Replace every match of a packed HOST batch.  Per chunk of rows (36 bytes per row: offset, count, match offset, length, output offset):
+// upload, count pass, prefix sum here; then in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of matches: CSR fill, lengths, prefix sum
+// here into the caller's out_offsets; then, while the caller's buffer has room, in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of
+// output text: splice and download.  The offsets handed to the device are rebased to each sub-range.
+int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_view *v, const void *repl, uint32_t repl_len, uint64_t *out_offsets,
+                                   void *out_data, uint64_t capacity, uint64_t *total) {
+    const char *who = "replace_all_packed_host";
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!out_offsets || !total || (capacity && !out_data)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (repl_len > NEEDLE_REPLACE_MAX_UNITS) return fail(NEEDLE_ERR_INVALID, "replacement longer than NEEDLE_REPLACE_MAX_UNITS code units");
+    if (repl_len && !repl) return fail(NEEDLE_ERR_INVALID, "replacement is NULL");
+    out_offsets[0] = 0;
+    *total = 0;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if ((rc = check_packed_rows(v, ~0ull, ""))) return rc;
+    const uint64_t cw = v->char_width;
+    struct At {
+        uint64_t cnt, moff, len, ooff;
+    };
+    std::vector<uint32_t> counts;
+    std::vector<uint64_t> moff, lens, local;
+    bool room = true; // the output so far fits the caller's buffer
+    rc = for_packed_chunks(
+        v, 8 + 4 + 8 + 8 + 8, 1, who,
+        [&](Slab &lay, uint64_t nr) {
+            const uint64_t cnt = lay.add(nr * 4), mo = lay.add((nr + 1) * 8), len = lay.add(nr * 8);
+            return At{cnt, mo, len, lay.add((nr + 1) * 8)};
+        },
+        [&](const needle_packed_view &dv, const ChunkOut &out, uint64_t r0, const At &o) {
+            const uint64_t nr = dv.n_rows;
+            int rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(out.d + o.cnt), nullptr);
+            moff.assign(nr + 1, 0);
+            if (rc || (rc = csr_offsets(out, o.cnt, 0, nr, counts, moff.data()))) return rc;
+            uint64_t *d_moff = (uint64_t *)(out.d + o.moff), *d_len = (uint64_t *)(out.d + o.len), *d_ooff = (uint64_t *)(out.d + o.ooff);
+            const std::vector<RowRange> ranges = csr_ranges(moff.data(), 0, nr, std::max<uint64_t>(host_result_bytes() / 8, 1));
+            uint64_t biggest = 0;
+            for (const RowRange &rg : ranges) biggest = std::max<uint64_t>(biggest, moff[rg.second] - moff[rg.first]);
+            Slab lay;
+            const uint64_t o_s = lay.add(biggest * 4), o_e = lay.add(biggest * 4);
+            DevSlab list;
+            hipError_t e = list.alloc(lay.total());
+            if (e != hipSuccess) return hip_fail(e, "replace_all_packed_host matches");
+            int32_t *d_s = (int32_t *)(list.d + o_s), *d_e = (int32_t *)(list.d + o_e);
+            for (const RowRange &rg : ranges) {
+                const uint64_t a = rg.first, sn = rg.second - rg.first;
+                local.resize(sn + 1);
+                for (uint64_t r = 0; r <= sn; ++r) local[r] = moff[a + r] - moff[a];
+                HIP_TRY(hipMemcpy(d_moff, local.data(), (sn + 1) * 8, hipMemcpyHostToDevice));
+                needle_packed_view sv = dv;
+                sv.offsets = dv.offsets + a;
+                sv.n_rows = sn;
+                int more = 0;
+                if (local[sn] && (rc = needle_find_all_csr_packed_dev(p, &sv, d_moff, d_s, d_e, &more, nullptr))) return rc;
+                if (more) return fail(NEEDLE_ERR_DEVICE, "replace_all_packed_host: count pass and fill pass disagree");
+                if ((rc = needle_replace_all_lengths_packed_dev(&sv, d_moff, d_s, d_e, repl_len, d_len, nullptr))) return rc;
+                lens.resize(sn);
+                if ((rc = out.download(lens.data(), o.len, sn * 8))) return rc;
+                uint64_t *oo = out_offsets + r0 + a;
+                for (uint64_t r = 0; r < sn; ++r) oo[r + 1] = oo[r] + lens[r];
+                if (!room || oo[sn] > capacity) {
+                    room = false;
+                    continue;
+                }
+                const std::vector<RowRange> pieces = csr_ranges(out_offsets, r0 + a, r0 + a + sn, std::max<uint64_t>(host_result_bytes() / cw, 1));
+                uint64_t most = 0;
+                for (const RowRange &pc : pieces) most = std::max<uint64_t>(most, out_offsets[pc.second] - out_offsets[pc.first]);
+                DevSlab text;
+                if ((e = text.alloc(most * cw)) != hipSuccess) return hip_fail(e, "replace_all_packed_host text");
+                for (const RowRange &pc : pieces) {
+                    const uint64_t x = pc.first - r0, pn = pc.second - pc.first, units = out_offsets[pc.second] - out_offsets[pc.first];
+                    if (!units) continue;
+                    local.resize(pn + 1);
+                    for (uint64_t r = 0; r <= pn; ++r) local[r] = out_offsets[pc.first + r] - out_offsets[pc.first];
+                    HIP_TRY(hipMemcpy(d_ooff, local.data(), (pn + 1) * 8, hipMemcpyHostToDevice));
+                    needle_packed_view tv = dv;
+                    tv.offsets = dv.offsets + x;
+                    tv.n_rows = pn;
+                    if ((rc = needle_replace_all_fill_packed_dev(&tv, d_moff + (x - a), d_s, d_e, repl, repl_len, d_ooff, text.d, nullptr))) return rc;
+                    e = hipMemcpy((uint8_t *)out_data + out_offsets[pc.first] * cw, text.d, units * cw, hipMemcpyDeviceToHost);
+                    if (e != hipSuccess) return hip_fail(e, "replace_all_packed_host download");
+                }
+            }
+            return (int)NEEDLE_OK;
+        });
+    if (rc == NEEDLE_OK) *total = out_offsets[v->n_rows];
+    return rc;
+}
+
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------

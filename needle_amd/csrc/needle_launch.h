@@ -8,6 +8,7 @@
 #include "needle_device.h"
 #include "needle_find_all.h"
 #include "needle_ngram.h"
+#include "needle_replace.h"
 
 namespace needle {
 
@@ -68,6 +69,10 @@ size_t ngram_packed_find_all_lds_bytes(const ProgHeader &h, const NgramParams &n
 hipError_t launch_ngram_packed_find_all(const ScanArgs &a, const uint64_t *row_offsets, const NgramParams &ng, const uint32_t *d_bitmap, uint32_t *d_stats,
                                         uint32_t *counts, int32_t *starts, int32_t *ends, int32_t *more, const uint64_t *offsets, bool count_only, int n_cus,
                                         hipStream_t stream, int char_width, int page, int sub);
+// needle_replace.hip: the splice of needle_replace_all_*_packed_dev (lengths, fill) and the replacement's way to the device
+hipError_t launch_replace_put(const void *repl_host, uint32_t bytes, uint8_t *d_repl, hipStream_t stream);
+hipError_t launch_replace_lengths(const ReplaceArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_replace_fill(const ReplaceArgs &a, int n_cus, hipStream_t stream);
 // needle_lower.cpp (NEEDLE_PREFILTER)
 int ngram_level();
 

@@ -1014,6 +1014,127 @@ class Pattern:
         off, st, en = self.find_all_packed(data, offsets)
         return [list(zip(st[off[i]:off[i + 1]].tolist(), en[off[i]:off[i + 1]].tolist())) for i in range(len(strings))]
 
+    # ---- replace every match of every packed row (needle_replace_all_*_packed_dev / needle_replace_all_packed_host)
+    @staticmethod
+    def _repl_units(repl, char_width):
+        """The replacement as code units of the rows' width: a str (UTF-16 code units; for 8-bit rows every char must be below 256) or a
+        1-D array of code units.  It is literal: no group references."""
+        dt = np.uint8 if char_width == 1 else np.uint16
+        u = _utf16(repl) if isinstance(repl, str) else np.ascontiguousarray(repl)
+        assert u.ndim == 1, "repl: str or 1-D array of code units"
+        if u.size and (int(u.min()) < 0 or int(u.max()) > (255 if char_width == 1 else 65535)):
+            raise ValueError("replacement holds a code unit that %d-byte rows cannot hold" % char_width)
+        if u.size > _lib.REPLACE_MAX_UNITS:
+            raise ValueError("replacement longer than %d code units" % _lib.REPLACE_MAX_UNITS)
+        return np.ascontiguousarray(u.astype(dt))
+
+    @staticmethod
+    def splice_packed(data, offsets, match_offsets, start, end, repl, stream=None, out=None, out_start=0):
+        """The two pattern-free entries (needle_replace_all_lengths_packed_dev, torch cumsum, needle_replace_all_fill_packed_dev) on one
+        stream: every match of the caller's CSR list (match_offsets int64[n + 1], start / end int32, positions relative to the row,
+        monotone within each row -- find_all_packed's result, or a subset of it) replaced by `repl` -> (out_data, out_offsets int64[n + 1]).
+        out: optional caller-owned tensor of the rows' dtype; the result then starts at its code unit out_start (appending) and out_offsets
+        are positions in `out`; units outside [out_offsets[0], out_offsets[n]) are left as they are.  The one host read is the total.
+        numpy inputs are uploaded, spliced on the device and brought back."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.uint16:
+                data = data.view(np.int16)
+            dev = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x).astype(dt)).to("cuda")
+            o, oo = Pattern.splice_packed(dev(np.concatenate([data, np.zeros((-data.nbytes) % 4 // data.itemsize, data.dtype)]), data.dtype),
+                                          dev(offsets, np.int64), dev(match_offsets, np.int64), dev(start, np.int32), dev(end, np.int32), repl, stream)
+            o = o.cpu().numpy()
+            return (o.view(np.uint16) if o.dtype == np.int16 else o), oo.cpu().numpy()
+        assert data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), "data: 1-D uint8 or (u)int16 code units"
+        for t, dt, what in ((offsets, torch.int64, "offsets"), (match_offsets, torch.int64, "match_offsets"), (start, torch.int32, "start"), (end, torch.int32, "end")):
+            assert isinstance(t, torch.Tensor) and t.device == data.device and t.dtype == dt and t.dim() == 1 and t.is_contiguous(), what
+        n, dv, cw = offsets.numel() - 1, data.device, data.element_size()
+        assert n >= 0 and match_offsets.numel() == n + 1 and start.numel() == end.numel()
+        r = Pattern._repl_units(repl, cw)
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), cw, n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            s = one.cuda_stream
+            sp, ep = (start.data_ptr(), end.data_ptr()) if start.numel() else (None, None)
+            lens = torch.empty(n, dtype=torch.int64, device=dv)
+            _check(L.needle_replace_all_lengths_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, r.size, lens.data_ptr(), s))
+            out_off = torch.full((n + 1,), int(out_start), dtype=torch.int64, device=dv)
+            if n:
+                out_off[1:] += torch.cumsum(lens, 0)
+            total = int(out_off[-1].item())
+            if out is None:
+                out = torch.empty(total + 4, dtype=data.dtype, device=dv)[:total]  # (never an empty allocation: its pointer would be NULL)
+            else:
+                assert out.device == dv and out.dtype == data.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= total
+            _check(L.needle_replace_all_fill_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, r.ctypes.data if r.size else None, r.size,
+                                                        out_off.data_ptr(), out.data_ptr(), s))
+        return out, out_off
+
+    def replace_all_packed(self, data, offsets, repl, stream=None, out=None, out_start=0):
+        """Every non-overlapping match of every packed row -- the matches find_all_packed files -- replaced by the literal `repl` (a str, or a
+        1-D array of code units) -> (out_data, out_offsets[n + 1]): row r's result is out_data[out_offsets[r]:out_offsets[r + 1]].  What a
+        caller gets who loops the reference's find() and appends to a StringBuilder (an empty match is replaced once and ends its row);
+        not java.util.regex's replaceAll for nullable patterns.  Device tensors: find_all_packed's count / cumsum / fill, then splice_packed
+        (lengths, cumsum, fill), all on one stream; the host reads the two totals.  out / out_start: as splice_packed.  numpy data + offsets:
+        needle_replace_all_packed_host."""
+        L = _lib.lib()
+        if isinstance(data, np.ndarray) or not (type(data).__module__.startswith("torch") and data.is_cuda):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.int16:
+                data = data.view(np.uint16)
+            assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            r = Pattern._repl_units(repl, data.dtype.itemsize)
+            v = _lib.PackedView()
+            v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+            out_off = np.zeros(n + 1, dtype=np.uint64)
+            capacity = max(1024, 2 * int(offsets[-1] - offsets[0]))
+            while True:  # (first with a guessed capacity, then with the exact total)
+                text = np.empty(capacity, dtype=data.dtype)
+                total = ctypes.c_uint64(0)
+                _check(L.needle_replace_all_packed_host(self._h, ctypes.byref(v), r.ctypes.data if r.size else None, r.size, out_off.ctypes.data,
+                                                        text.ctypes.data, capacity, ctypes.byref(total)))
+                if total.value <= capacity:
+                    return text[:total.value], out_off.astype(np.int64)
+                capacity = int(total.value)
+        off, st, en = self.find_all_packed(data, offsets, stream=stream)
+        return Pattern.splice_packed(data, offsets, off, st, en, repl, stream=stream, out=out, out_start=out_start)
+
+    def replace_first_packed(self, data, offsets, repl, stream=None, out=None, out_start=0):
+        """The first match of every packed row (find_packed's) replaced by `repl` -> (out_data, out_offsets): find_packed's results turned
+        into a list of at most one match per row (cumsum of the matched bits), then splice_packed.  numpy inputs are uploaded first."""
+        import torch
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.uint16:
+                data = data.view(np.int16)
+            pad = np.zeros((-data.nbytes) % 4 // data.itemsize, data.dtype)
+            o, oo = self.replace_first_packed(torch.from_numpy(np.concatenate([data, pad])).to("cuda"),
+                                              torch.from_numpy(np.ascontiguousarray(offsets).astype(np.int64)).to("cuda"), repl, stream)
+            o = o.cpu().numpy()
+            return (o.view(np.uint16) if o.dtype == np.int16 else o), oo.cpu().numpy()
+        dv, n = data.device, offsets.numel() - 1
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            words, st, en = self.find_packed(data, offsets, stream=stream)
+            hit = ((words.unsqueeze(1) >> torch.arange(64, device=dv)) & 1).reshape(-1)[:n].bool()
+            moff = torch.zeros(n + 1, dtype=torch.int64, device=dv)
+            if n:
+                torch.cumsum(hit, 0, out=moff[1:])
+            st1, en1 = st[:n][hit].contiguous(), en[:n][hit].contiguous()
+        return Pattern.splice_packed(data, offsets, moff, st1, en1, repl, stream=stream, out=out, out_start=out_start)
+
+    def replace_all_strings(self, strings, repl):
+        """Every match of every str replaced by the str `repl` -> list[str] (UTF-16 code units, like java.lang.String): pack_strings +
+        replace_all_packed, the counterpart of find_all_strings."""
+        data, offsets = pack_strings(strings)
+        text, off = self.replace_all_packed(data, offsets, repl)
+        return [text[off[i]:off[i + 1]].tobytes().decode("utf-16-le", "surrogatepass") for i in range(len(strings))]
+
     @staticmethod
     def rows_from_packed(data, offsets, row_stride=None, stream=None):
         """Device tensors: packed code units (1-D uint8 | int16) + int64 offsets[n + 1] -> (rows [n, row_stride],

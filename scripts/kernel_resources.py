@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """VGPRs / scratch of every instantiation of the tiled scan kernel, of the per-lane and the lock-step find-all kernels of fixed-stride
 rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel
-and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip)
+and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
+(needle_replace.hip: 4 waves per workgroup, static LDS)
 (cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
 LDS is the program plus one window (the tile) per wave, sized at launch: listed as the window per wave.
@@ -20,11 +21,12 @@ for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", 
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
            "needle_packed_set1", "needle_packed_set2",
            "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2",
-           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2"):
+           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
                                          "-S", "-o", out, os.path.join(CSRC, tu + ".hip")], stderr=subprocess.DEVNULL)))
 rows = []
+lds = {}  # static LDS bytes per kernel (the replace kernels' tables; the other kernels size their LDS at launch)
 for out, pr in procs:
     pr.wait()
     k = None
@@ -36,6 +38,9 @@ for out, pr in procs:
         m = re.match(r"\s+\.amdhsa_private_segment_fixed_size\s+(\d+)", line)
         if m and k:
             k[1] = int(m.group(1))
+        m = re.match(r"\s+\.amdhsa_group_segment_fixed_size\s+(\d+)", line)
+        if m and k:
+            lds[k[0]] = int(m.group(1))
         m = re.match(r"\s+\.amdhsa_next_free_vgpr\s+(\d+)", line)
         if m and k:
             k[2] = int(m.group(1))
@@ -88,3 +93,9 @@ for title, rx in (("n-gram filter kernels, fixed-stride rows (needle_ngram.hip):
         if m:
             print("%4d %4d  %-11s %-8s S%s cw%s %s%s" % (sc, v, names_ng[m.group(1)], modes[m.group(2)], m.group(3), m.group(4), "wide " if m.group(5) == "1" else "",
                                                        "backward-walks" if m.lastindex >= 6 and m.group(6) == "1" else ""))
+# the replace kernels (needle_replace.hip): the lengths kernel, the fill kernel per char width, the replacement's upload
+print("replace kernels (needle_replace.hip): scratch bytes / VGPRs / LDS bytes per workgroup / kernel")
+for k, sc, v in sorted(rows):
+    m = re.search(r"replace_(lengths|fill|put)_kernel(?:ILi(\d)E)?", k)
+    if m:
+        print("%4d %4d %6d  replace %-8s %s" % (sc, v, lds.get(k, 0), m.group(1), "cw" + m.group(2) if m.group(2) else ""))
