@@ -53,6 +53,62 @@ public final class GpuPatternSet implements AutoCloseable {
         return masks;
     }
 
+    /** Result of {@link #tagMatchesStrings}: haystack r's matches are start / end / masks[offsets[r] .. offsets[r + 1]). */
+    public static final class TaggedMatches {
+        public final long[] offsets;
+        public final int[] start;
+        public final int[] end;
+        /** bit j of masks[m]: pattern j matches() the text of match m as a whole. */
+        public final int[] masks;
+
+        TaggedMatches(long[] offsets, int[] start, int[] end, int[] masks) {
+            this.offsets = offsets;
+            this.start = start;
+            this.end = end;
+            this.masks = masks;
+        }
+
+        /** The lowest set bit of masks[m] -- the convention for "the rule" of a match of a union compiled in member order -- or -1. */
+        public int firstMember(int m) {
+            return masks[m] == 0 ? -1 : Integer.numberOfTrailingZeros(masks[m]);
+        }
+    }
+
+    /**
+     * Every non-overlapping match of {@code pattern} (typically the union (r0)|(r1)|.. of this set's rules) in every haystack, with the
+     * mask of this set's patterns that match it (needle_set_tag_matches_packed_host): a sizing call, then the lists.
+     */
+    public TaggedMatches tagMatchesStrings(GpuPattern pattern, String[] haystacks) {
+        long[] offsets = new long[haystacks.length + 1];
+        for (int i = 0; i < haystacks.length; i++) {
+            offsets[i + 1] = offsets[i] + haystacks[i].length();
+        }
+        char[] data = new char[(int) offsets[haystacks.length]];
+        for (int i = 0; i < haystacks.length; i++) {
+            haystacks[i].getChars(0, haystacks[i].length(), data, (int) offsets[i]);
+        }
+        long[] matchOffsets = new long[haystacks.length + 1];
+        long[] total = new long[1];
+        GpuPattern.check(Native.setTagMatchesPackedHost(handle, pattern.handle(), data, offsets, matchOffsets, null, null, null, total), "(pattern set)");
+        int[] start = new int[(int) total[0]];
+        int[] end = new int[(int) total[0]];
+        int[] masks = new int[(int) total[0]];
+        if (total[0] > 0) {
+            GpuPattern.check(Native.setTagMatchesPackedHost(handle, pattern.handle(), data, offsets, matchOffsets, start, end, masks, total), "(pattern set)");
+        }
+        return new TaggedMatches(matchOffsets, start, end, masks);
+    }
+
+    /**
+     * needle_set_matches_spans_packed_dev for a host whose batch and match list are ALREADY in device memory: every argument but
+     * charWidth and nRows is a device address (data 4-byte aligned; offsets and spanOffsets nRows + 1 uint64; start / end int32 relative
+     * to the row, 0 only when there are no spans; masks uint32 indexed like start), stream a hipStream_t (0: the null stream).
+     * Stream-ordered, nothing is read back; spans are clamped into their rows and need not be sorted.
+     */
+    public void matchesSpans(long data, int charWidth, long nRows, long offsets, long spanOffsets, long start, long end, long masks, long stream) {
+        GpuPattern.check(Native.setMatchesSpansPackedDev(handle, data, charWidth, nRows, offsets, spanOffsets, start, end, masks, stream), "(pattern set)");
+    }
+
     @Override
     public void close() {
         if (handle != 0) {

@@ -84,6 +84,17 @@ final class Native {
 
     static native int setPackedHost(long set, int op, char[] data, long[] offsets, int[] masks);
 
+    /**
+     * needle_set_tag_matches_packed_host: findAllPackedHost of `pattern` with the set's mask of every match beside it; masks
+     * int[capacity] (start / end / masks null: count only).
+     */
+    static native int setTagMatchesPackedHost(long set, long pattern, char[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end,
+                                              int[] masks, long[] total);
+
+    /** needle_set_matches_spans_packed_dev: every long but nRows is a device address (stream: a hipStream_t). */
+    static native int setMatchesSpansPackedDev(long set, long data, int charWidth, long nRows, long offsets, long spanOffsets, long start,
+                                               long end, long masks, long stream);
+
     /** needle_find_all_host: counts int[nRows]; start / end int[nRows * maxPerRow]; more int[1]. */
     static native int findAllHost(long handle, java.nio.ByteBuffer rows, int charWidth, long nRows, long rowStride, int rowLen,
                                   java.nio.ByteBuffer lengths, int maxPerRow, int[] counts, int[] start, int[] end, int[] more);

@@ -463,6 +463,57 @@ NATIVE(jint, setPackedHost)(JNIEnv *env, jclass c, jlong s, jint op, jcharArray 
     return rc;
 }
 
+/* needle_set_tag_matches_packed_host: as findAllPackedHost, masks beside start / end (all three null: count only). */
+NATIVE(jint, setTagMatchesPackedHost)(JNIEnv *env, jclass c, jlong s, jlong h, jcharArray data, jlongArray offsets, jlongArray matchOffsets,
+                                      jintArray start, jintArray end, jintArray masks, jlongArray total) {
+    if (!data || !offsets || !matchOffsets || !total) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, matchOffsets) < n1 || (*env)->GetArrayLength(env, total) < 1) return NEEDLE_ERR_INVALID;
+    jsize cap = start && end && masks ? (*env)->GetArrayLength(env, start) : 0;
+    if (cap && (*env)->GetArrayLength(env, end) < cap) cap = (*env)->GetArrayLength(env, end);
+    if (cap && (*env)->GetArrayLength(env, masks) < cap) cap = (*env)->GetArrayLength(env, masks);
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong *mo = (*env)->GetLongArrayElements(env, matchOffsets, NULL);
+    jint *st = cap ? (*env)->GetIntArrayElements(env, start, NULL) : NULL;
+    jint *en = cap ? (*env)->GetIntArrayElements(env, end, NULL) : NULL;
+    jint *mk = cap ? (*env)->GetIntArrayElements(env, masks, NULL) : NULL;
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    uint64_t t = 0;
+    int rc = needle_set_tag_matches_packed_host((const needle_pattern_set *)(intptr_t)s, (const needle_pattern *)(intptr_t)h, &v, (uint64_t *)mo,
+                                                (int32_t *)st, (int32_t *)en, (uint32_t *)mk, (uint64_t)cap, &t);
+    jlong jt = (jlong)t;
+    (*env)->SetLongArrayRegion(env, total, 0, 1, &jt);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, matchOffsets, mo, 0);
+    if (st) (*env)->ReleaseIntArrayElements(env, start, st, 0);
+    if (en) (*env)->ReleaseIntArrayElements(env, end, en, 0);
+    if (mk) (*env)->ReleaseIntArrayElements(env, masks, mk, 0);
+    return rc;
+}
+
+/* needle_set_matches_spans_packed_dev: device addresses as jlong. */
+NATIVE(jint, setMatchesSpansPackedDev)(JNIEnv *env, jclass c, jlong s, jlong data, jint charWidth, jlong nRows, jlong offsets, jlong spanOffsets,
+                                       jlong start, jlong end, jlong masks, jlong stream) {
+    (void)env;
+    if (nRows < 0) return NEEDLE_ERR_INVALID;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    v.data = (const void *)(intptr_t)data;
+    v.char_width = (uint32_t)charWidth;
+    v.n_rows = (uint64_t)nRows;
+    v.offsets = (const uint64_t *)(intptr_t)offsets;
+    return needle_set_matches_spans_packed_dev((const needle_pattern_set *)(intptr_t)s, &v, (const uint64_t *)(intptr_t)spanOffsets,
+                                               (const int32_t *)(intptr_t)start, (const int32_t *)(intptr_t)end, (uint32_t *)(intptr_t)masks,
+                                               (void *)(intptr_t)stream);
+}
+
 NATIVE(jbyteArray, serialize)(JNIEnv *env, jclass c, jlong h) {
     size_t need = 0;
     const needle_pattern *p = (const needle_pattern *)(intptr_t)h;

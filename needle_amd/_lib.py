@@ -23,6 +23,7 @@ EXPORTS = [
     "needle_replace_all_lengths_packed_dev", "needle_replace_all_fill_packed_dev", "needle_replace_all_packed_host",
     "needle_pattern_set_create", "needle_pattern_set_destroy", "needle_pattern_set_info", "needle_pattern_set_get_tables",
     "needle_set_matches_packed_dev", "needle_set_contained_in_packed_dev", "needle_set_matches_packed_host", "needle_set_contained_in_packed_host",
+    "needle_set_matches_spans_packed_dev", "needle_set_tag_matches_packed_host",
     "needle_multi_create", "needle_multi_destroy", "needle_multi_device_count", "needle_multi_stream", "needle_multi_transport", "needle_multi_scan",
     "needle_multi_sync", "needle_scan_host_multi", "needle_multi_unique_id", "needle_multi_create_rank",
     "needle_multi_all_gather_u64", "needle_multi_gather_i32",
@@ -174,6 +175,8 @@ def lib():
         getattr(L, n).argtypes = [VP, P(PackedView), VP, VP]
     for n in ("needle_set_matches_packed_host", "needle_set_contained_in_packed_host"):
         getattr(L, n).argtypes = [VP, P(PackedView), VP]
+    L.needle_set_matches_spans_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP, VP]
+    L.needle_set_tag_matches_packed_host.argtypes = [VP, VP, P(PackedView), VP, VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]
     L.needle_matcher_create.argtypes = [VP, VP, ctypes.c_size_t, P(VP)]
     L.needle_matcher_destroy.argtypes = [VP]
     L.needle_matcher_destroy.restype = None

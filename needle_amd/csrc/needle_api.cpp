@@ -2457,4 +2457,40 @@ int needle_set_contained_in_packed_dev(const needle_pattern_set *s, const needle
     return run_set_packed_dev(s, OP_CONTAINED_IN, v, d_masks, stream);
 }
 
+// Which members match each span of a CSR span list (needle_set_spans.h): a pure function of (text, list, set).  The checks and the
+// group loop of run_set_packed_dev: one launch per group on the caller's stream, group 0 stores, later groups OR.
+int needle_set_matches_spans_packed_dev(const needle_pattern_set *cs, const needle_packed_view *v, const uint64_t *d_span_offsets,
+                                        const int32_t *d_start, const int32_t *d_end, uint32_t *d_masks, void *stream_) {
+    needle_pattern_set *s = const_cast<needle_pattern_set *>(cs);
+    if (!s) return fail(NEEDLE_ERR_INVALID, "pattern set is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!d_span_offsets) return fail(NEEDLE_ERR_INVALID, "span offsets is NULL");
+    if (!d_masks) return fail(NEEDLE_ERR_INVALID, "masks is NULL");
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    const int cw = (int)v->char_width;
+    if ((rc = set_plan_usable(s, OP_MATCHES, cw))) return rc;
+    const SetPlan &plan = s->plan[OP_MATCHES][cw - 1];
+    for (size_t g = 0; g < plan.groups.size(); ++g) {
+        const uint8_t *d_blob = nullptr;
+        int n_cus = 0;
+        if ((rc = set_program(s, OP_MATCHES, cw, (int)g, &d_blob, &n_cus))) return rc;
+        SetSpansArgs a;
+        memset(&a, 0, sizeof(a));
+        a.rows = (const uint8_t *)v->data;
+        a.offsets = v->offsets;
+        a.n_rows = v->n_rows;
+        a.prog = d_blob;
+        a.hdr = plan.groups[g].prog.hdr;
+        a.span_off = d_span_offsets;
+        a.start = d_start;
+        a.end = d_end;
+        a.masks = d_masks;
+        a.store = g == 0 ? 1u : 0u;
+        HIP_TRY(launch_set_spans(cw, a, n_cus, (hipStream_t)stream_));
+    }
+    return NEEDLE_OK;
+}
+
 } // extern "C"

@@ -165,6 +165,20 @@ struct PackedSetArgs {
     uint32_t store;       // != 0: masks[r] = the group's bits (the set's first group); 0: masks[r] |= them (stream-ordered, one lane per row)
 };
 
+// The pattern-set kernel of a CSR span list over packed rows (needle_set_spans.h): one launch per group of the set.
+struct SetSpansArgs {
+    const uint8_t *rows;      // the view's data (device, 4-byte aligned)
+    const uint64_t *offsets;  // n_rows + 1 row offsets, in code units
+    uint64_t n_rows;
+    const uint8_t *prog;      // the group's OP_MATCHES program (lower_pattern_set) and its header
+    ProgHeader hdr;
+    const uint64_t *span_off; // n_rows + 1: row r's spans are start / end[span_off[r] .. span_off[r + 1])
+    const int32_t *start, *end; // relative to the row, in code units
+    uint32_t *masks;          // indexed like start
+    uint32_t store;           // != 0: masks[m] = the group's bits (the set's first group); 0: masks[m] |= them
+};
+constexpr uint32_t kSetSpansWaveLds = 2u * 65u * 8u; // a wave's 65 span offsets + 65 row offsets behind the program
+
 // Long rows of table-mode automata (needle_stripe.hip, "speculative stripes"): every stripe is first scanned as a row of
 // its own from the START state (the tiled kernel, all stripes in parallel); then each stripe whose true entry state
 // differs is re-walked next to the speculative run until the two states meet.

@@ -461,14 +461,16 @@ static int run_set_packed_host(const needle_pattern_set *s, int op, const needle
 // that the results resident on the device stay bounded too (NEEDLE_HOST_RESULT_BYTES): a dense-match batch (a one-char pattern over
 // 256-char rows files ~2 KiB per row) would otherwise ask for several times the chunk's row bytes in one allocation.
 // fill(a, n, d_csr, d_start, d_end, &more): the layout's fill of rows [a, a + n) at the sub-range's own offsets, uploaded to d_csr.
-template <class Fill>
+// masks != nullptr (needle_set_tag_matches_packed_host): a third result array of 4 bytes per match -- tag(a, n, d_csr, d_start, d_end,
+// d_masks) fills it behind the fill, and it is downloaded with the other two.
+template <class Fill, class Tag>
 static int csr_fill_pass(const std::string &who, const uint64_t *offsets, uint64_t r0, uint64_t r1, uint8_t *d_csr, int32_t *start, int32_t *end,
-                         Fill &&fill) {
-    const std::vector<RowRange> ranges = csr_ranges(offsets, r0, r1, std::max<uint64_t>(host_result_bytes() / 8, 1));
+                         Fill &&fill, uint32_t *masks, Tag &&tag) {
+    const std::vector<RowRange> ranges = csr_ranges(offsets, r0, r1, std::max<uint64_t>(host_result_bytes() / csr_match_bytes(masks != nullptr), 1));
     uint64_t biggest = 0;
     for (const RowRange &rg : ranges) biggest = std::max<uint64_t>(biggest, offsets[rg.second] - offsets[rg.first]);
     Slab lay;
-    const uint64_t o_s = lay.add(biggest * 4), o_e = lay.add(biggest * 4);
+    const uint64_t o_s = lay.add(biggest * 4), o_e = lay.add(biggest * 4), o_m = lay.add(masks ? biggest * 4 : 0);
     DevSlab dev;
     hipError_t e = dev.alloc(lay.total());
     if (e != hipSuccess) return hip_fail(e, (who + " results").c_str());
@@ -484,11 +486,20 @@ static int csr_fill_pass(const std::string &who, const uint64_t *offsets, uint64
         int rc = fill(a, sn, (const uint64_t *)d_csr, (int32_t *)(dev.d + o_s), (int32_t *)(dev.d + o_e), &more);
         if (rc) return rc;
         if (more) return fail(NEEDLE_ERR_DEVICE, who + ": count pass and fill pass disagree");
+        if (masks && (rc = tag(a, sn, (const uint64_t *)d_csr, (const int32_t *)(dev.d + o_s), (const int32_t *)(dev.d + o_e), (uint32_t *)(dev.d + o_m))))
+            return rc;
         e = hipMemcpy(start + offsets[a], dev.d + o_s, m * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(end + offsets[a], dev.d + o_e, m * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && masks) e = hipMemcpy(masks + offsets[a], dev.d + o_m, m * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_fail(e, (who + " download").c_str());
     }
     return NEEDLE_OK;
+}
+template <class Fill>
+static int csr_fill_pass(const std::string &who, const uint64_t *offsets, uint64_t r0, uint64_t r1, uint8_t *d_csr, int32_t *start, int32_t *end,
+                         Fill &&fill) {
+    return csr_fill_pass(who, offsets, r0, r1, d_csr, start, end, fill, nullptr,
+                         [](uint64_t, uint64_t, const uint64_t *, const int32_t *, const int32_t *, uint32_t *) { return (int)NEEDLE_OK; });
 }
 
 // The sections of a CSR chunk: the counts of its n rows, and the offsets of the fill pass's current sub-range.
@@ -641,34 +652,58 @@ int needle_find_all_csr_host(const needle_pattern *p, const needle_batch_view *v
 
 // The packed batch in host memory: row chunks of at most NEEDLE_HOST_CHUNK_BYTES of text (12 bytes per row: offset + count) are uploaded,
 // counted, the prefix sum built here, filled (in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of results) and downloaded.
-int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
-                                    uint64_t capacity, uint64_t *total) {
+// set != NULL (needle_set_tag_matches_packed_host): every match's member mask beside it, tagged on the device while the rows are resident.
+static int find_all_csr_packed_host(const char *who, const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *start,
+                                    int32_t *end, uint64_t capacity, uint64_t *total, const needle_pattern_set *set, uint32_t *masks) {
     if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
     int rc = check_packed(v);
     if (rc) return rc;
-    if (!offsets || !total || (capacity && (!start || !end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (!offsets || !total || (capacity && (!start || !end || (set && !masks)))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
     offsets[0] = 0;
     *total = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
+    if (set && (rc = set_plan_usable(set, OP_MATCHES, (int)v->char_width))) return rc;
     if ((rc = check_packed_rows(v, ~0ull, ""))) return rc;
     std::vector<uint32_t> counts;
     rc = for_packed_chunks(
-        v, 12, 1, "find_all_csr_packed_host", csr_sections,
+        v, 12, 1, who, csr_sections,
         [&](const needle_packed_view &dv, const ChunkOut &out, uint64_t r0, const CsrAt &o) {
             const uint64_t r1 = r0 + dv.n_rows;
             int rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(out.d + o.cnt), nullptr);
             if (rc || (rc = csr_offsets(out, o.cnt, r0, dv.n_rows, counts, offsets))) return rc;
             if (offsets[r1] == offsets[r0] || offsets[r1] > capacity) return (int)NEEDLE_OK;
-            return csr_fill_pass("find_all_csr_packed_host", offsets, r0, r1, out.d + o.csr, start, end,
-                                 [&](uint64_t a, uint64_t sn, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
-                                     needle_packed_view sv = dv;
-                                     sv.offsets = dv.offsets + (a - r0);
-                                     sv.n_rows = sn;
-                                     return needle_find_all_csr_packed_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
-                                 });
+            auto sub = [&](uint64_t a, uint64_t sn) {
+                needle_packed_view sv = dv;
+                sv.offsets = dv.offsets + (a - r0);
+                sv.n_rows = sn;
+                return sv;
+            };
+            return csr_fill_pass(
+                who, offsets, r0, r1, out.d + o.csr, start, end,
+                [&](uint64_t a, uint64_t sn, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
+                    const needle_packed_view sv = sub(a, sn);
+                    return needle_find_all_csr_packed_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
+                },
+                set ? masks : nullptr,
+                [&](uint64_t a, uint64_t sn, const uint64_t *d_csr, const int32_t *d_s, const int32_t *d_e, uint32_t *d_m) {
+                    const needle_packed_view sv = sub(a, sn);
+                    return needle_set_matches_spans_packed_dev(set, &sv, d_csr, d_s, d_e, d_m, nullptr);
+                });
         });
     if (rc == NEEDLE_OK) *total = offsets[v->n_rows];
     return rc;
+}
+
+int needle_find_all_csr_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *start, int32_t *end,
+                                    uint64_t capacity, uint64_t *total) {
+    return find_all_csr_packed_host("find_all_csr_packed_host", p, v, offsets, start, end, capacity, total, nullptr, nullptr);
+}
+
+// Every match of `p` in every row with the mask of the set's members that match it whole (needle_set_matches_spans_packed_dev).
+int needle_set_tag_matches_packed_host(const needle_pattern_set *s, const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets,
+                                       int32_t *start, int32_t *end, uint32_t *masks, uint64_t capacity, uint64_t *total) {
+    if (!s) return fail(NEEDLE_ERR_INVALID, "pattern set is NULL");
+    return find_all_csr_packed_host("set_tag_matches_packed_host", p, v, offsets, start, end, capacity, total, s, masks);
 }
 
 // Replace every match of a packed HOST batch.  Per chunk of rows (36 bytes per row: offset, count, match offset, length, output offset):

@@ -37,6 +37,10 @@ inline std::vector<RowRange> packed_chunks(const uint64_t *offsets, uint64_t n_r
     return chunks;
 }
 
+// Device bytes of one match of a CSR fill pass: int32 start + end, and a uint32 mask beside them where the matches are tagged by a
+// pattern set (needle_set_tag_matches_packed_host).
+inline uint64_t csr_match_bytes(bool tagged) { return tagged ? 12 : 8; }
+
 // The row ranges of a CSR fill pass over rows [r0, r1), whose match counts stand summed up in `offsets`: at least one row each, at most
 // max_m matches (one row may exceed it).
 inline std::vector<RowRange> csr_ranges(const uint64_t *offsets, uint64_t r0, uint64_t r1, uint64_t max_m) {

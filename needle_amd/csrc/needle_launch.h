@@ -25,6 +25,8 @@ bool packed_find_all_lane_mode(uint32_t mode);
 bool packed_find_all_lane_shape(uint32_t prog_lds_bytes, int char_width, int *waves, int *chb);
 // needle_packed_set2.hip: a pattern set's group on packed rows (needle_packed_set.h); op: OP_MATCHES | OP_CONTAINED_IN
 hipError_t launch_packed_set(int op, int char_width, const PackedSetArgs &a, int n_cus, hipStream_t stream);
+// needle_set_spans2.hip: a pattern set's group on a CSR span list of packed rows (needle_set_spans.h): which members match each span
+hipError_t launch_set_spans(int char_width, const SetSpansArgs &a, int n_cus, hipStream_t stream);
 // needle_compact.hip
 int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
                       const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill);

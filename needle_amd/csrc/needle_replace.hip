@@ -25,6 +25,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "needle_csr_rows.h"
 #include "needle_launch.h"
 #include "needle_replace.h"
 
@@ -35,44 +36,12 @@ typedef uint32_t rp_u32x4 __attribute__((ext_vector_type(4)));
 // instructions: flat ones count on the LDS counter too and every piece-table read would wait for the loads in flight.
 #define RP_GLOBAL __attribute__((address_space(1)))
 
-// A wave's own LDS traffic is in order; this keeps the compiler from moving accesses across the hand-over between lanes.
-__device__ __forceinline__ void replace_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// (The wave's hand-over, the group's offsets in LDS, the row search and the clamp are needle_csr_rows.h's, shared with needle_set_spans.h.)
 __device__ __forceinline__ uint64_t replace_clamp(uint64_t x, uint64_t lo, uint64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// The group's 65 match offsets and 65 row offsets (rows beyond the batch: empty, with no matches) into the wave's LDS.
-__device__ __forceinline__ void replace_group_offsets(const ReplaceArgs &a, uint64_t g0, int lane, uint64_t *mo, uint64_t *ino) {
-    const uint64_t r = g0 + (uint64_t)lane < a.n_rows ? g0 + (uint64_t)lane : a.n_rows;
-    mo[lane] = a.match_off[r];
-    ino[lane] = a.in_off[r];
-    if (lane == 0) {
-        const uint64_t r2 = g0 + 64u < a.n_rows ? g0 + 64u : a.n_rows;
-        mo[64] = a.match_off[r2];
-        ino[64] = a.in_off[r2];
-    }
-}
-
-// The row (0 .. 63 within the group) of match m: the last r with mo[r] <= m.
-__device__ __forceinline__ uint32_t replace_row_of(const uint64_t *mo, uint64_t m) {
-    uint32_t r = 0;
-#pragma unroll
-    for (uint32_t step = 32; step; step >>= 1)
-        if (mo[r + step] <= m) r += step;
-    return r;
-}
 
 // Match m of row r (group-relative) clamped into its row: *s <= *e <= the row's length, in code units.
 __device__ __forceinline__ void replace_match(const ReplaceArgs &a, const uint64_t *ino, uint64_t m, uint32_t r, uint64_t *s, uint64_t *e) {
-    const uint64_t len = ino[r + 1] - ino[r];
-    const int32_t s32 = a.start[m], e32 = a.end[m];
-    const uint64_t sc = s32 < 0 ? 0ull : ((uint64_t)s32 > len ? len : (uint64_t)s32);
-    const uint64_t ec = e32 < 0 ? 0ull : ((uint64_t)e32 > len ? len : (uint64_t)e32);
-    *s = sc;
-    *e = ec < sc ? sc : ec;
+    csr_clamp(a.start[m], a.end[m], ino[r + 1] - ino[r], s, e);
 }
 
 __global__ __launch_bounds__(kReplaceWaves * 64) void replace_lengths_kernel(const ReplaceArgs a) {
@@ -85,23 +54,23 @@ __global__ __launch_bounds__(kReplaceWaves * 64) void replace_lengths_kernel(con
     const uint64_t n_groups = (a.n_rows + 63u) >> 6;
     for (uint64_t grp = (uint64_t)blockIdx.x * kReplaceWaves + (uint64_t)wave; grp < n_groups; grp += (uint64_t)gridDim.x * kReplaceWaves) {
         const uint64_t g0 = grp << 6;
-        replace_group_offsets(a, g0, lane, mo, ino);
+        csr_group_offsets(a.match_off, a.in_off, a.n_rows, g0, lane, mo, ino);
         sum[lane] = 0ull;
-        replace_wave_sync();
+        csr_wave_sync();
         const uint64_t m0 = mo[0], m1 = mo[64];
         for (uint64_t m = m0 + (uint64_t)lane; m < m1; m += 64u) {
-            const uint32_t r = replace_row_of(mo, m);
+            const uint32_t r = csr_row_of(mo, m);
             uint64_t s, e;
             replace_match(a, ino, m, r, &s, &e);
             atomicAdd(&sum[r], (unsigned long long)(e - s));
         }
-        replace_wave_sync();
+        csr_wave_sync();
         if (g0 + (uint64_t)lane < a.n_rows) {
             const uint64_t len = ino[lane + 1] - ino[lane], c = mo[lane + 1] - mo[lane];
             const uint64_t gone = sum[lane] < len ? sum[lane] : len;
             a.out_len[g0 + (uint64_t)lane] = len - gone + c * (uint64_t)a.repl_len;
         }
-        replace_wave_sync(); // (the next group overwrites the offsets)
+        csr_wave_sync(); // (the next group overwrites the offsets)
     }
 }
 
@@ -127,8 +96,8 @@ __global__ __launch_bounds__(kReplaceWaves * 64) void replace_fill_kernel(const 
     for (uint64_t grp = (uint64_t)blockIdx.x * kReplaceWaves + (uint64_t)wave; grp < n_groups; grp += (uint64_t)gridDim.x * kReplaceWaves) {
         const uint64_t g0 = grp << 6, g1 = g0 + 64u < n ? g0 + 64u : n;
         const uint64_t out_g0 = a.out_off[g0], out_g1 = a.out_off[g1]; // (with the other offsets: one round trip)
-        replace_group_offsets(a, g0, lane, mo, ino);
-        replace_wave_sync();
+        csr_group_offsets(a.match_off, a.in_off, a.n_rows, g0, lane, mo, ino);
+        csr_wave_sync();
         // the group's spans as absolute byte addresses, inside the batch's
         const uint64_t in_b = replace_clamp(ino[0], in_first, in_last), out_b = replace_clamp(out_g0, out_first, out_last);
         const uint64_t inB = dbase + in_b * CW, inE = dbase + replace_clamp(ino[64], in_b, in_last) * CW;
@@ -147,7 +116,7 @@ __global__ __launch_bounds__(kReplaceWaves * 64) void replace_fill_kernel(const 
                 long long delta = 0;
                 if (k < nk) {
                     const uint64_t m = mb + k;
-                    const uint32_t r = replace_row_of(mo, m);
+                    const uint32_t r = csr_row_of(mo, m);
                     uint64_t s, e;
                     replace_match(a, ino, m, r, &s, &e);
                     I = dbase + (ino[r] + s) * CW;
@@ -170,14 +139,14 @@ __global__ __launch_bounds__(kReplaceWaves * 64) void replace_fill_kernel(const 
                 uint64_t I = inE;
                 if (!last) {
                     const uint64_t m = mb + nk;
-                    const uint32_t r = replace_row_of(mo, m);
+                    const uint32_t r = csr_row_of(mo, m);
                     uint64_t s, e;
                     replace_match(a, ino, m, r, &s, &e);
                     I = dbase + (ino[r] + s) * CW;
                 }
                 O[nk] = I + D;
             }
-            replace_wave_sync();
+            csr_wave_sync();
             const uint64_t hi = last ? outE : replace_clamp(O[nk], lo, outE);
 
             // ---- sweep the chunk's output range [lo, hi): 64 lanes x 16 bytes a step.  A lane's 16 bytes are put together piece by piece
@@ -259,7 +228,7 @@ __global__ __launch_bounds__(kReplaceWaves * 64) void replace_fill_kernel(const 
                 }
             }
             lo = hi;
-            replace_wave_sync(); // (the next chunk, or the next group, overwrites the tables)
+            csr_wave_sync(); // (the next chunk, or the next group, overwrites the tables)
             if (last) break;
         }
     }

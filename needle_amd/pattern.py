@@ -1179,11 +1179,106 @@ class PatternSet:
         _check(_lib.lib().needle_pattern_set_create(arr, len(patterns), ctypes.byref(h)))
         self._h = h
         self.n_patterns = len(patterns)
+        self.members = [(p.regex, p.flags) for p in patterns]  # (regex source or None, flags) per member: union_pattern()
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None and _lib._lib is not None:
             _lib._lib.needle_pattern_set_destroy(h)
+
+    def union_pattern(self):
+        """The pattern (r0)|(r1)|.. of the members' regex sources in member order, compiled with their common flags: its find-all is
+        the span list that tag_matches_packed tags.  ValueError when a member has no regex source (from_tables, from_bytes) or the
+        members' flags differ."""
+        if any(r is None for r, _ in self.members):
+            raise ValueError("union_pattern: member %d has no regex source" % [r is None for r, _ in self.members].index(True))
+        flags = {f for _, f in self.members}
+        if len(flags) != 1:
+            raise ValueError("union_pattern: the members' flags differ")
+        return DFACompiler.compile("|".join("(" + r + ")" for r, _ in self.members), flags=flags.pop())
+
+    @staticmethod
+    def first_member(masks):
+        """Index of the lowest set bit of every mask, -1 for 0 (numpy or torch in, int32 numpy out).  For a union compiled in member
+        order (union_pattern) the lowest bit is the convention for "the rule" of a match: the first alternative that matches the span
+        whole, as an ordered rule list reads."""
+        m = masks.cpu().numpy() if not isinstance(masks, np.ndarray) and type(masks).__module__.startswith("torch") else np.asarray(masks)
+        m = np.ascontiguousarray(m).astype(np.int64) & 0xFFFFFFFF
+        low = m & -m
+        idx = np.zeros(m.shape, dtype=np.int32)
+        for b in (16, 8, 4, 2, 1):  # log2 of a power of two
+            hit = (low >> b) != 0
+            idx += np.where(hit, b, 0).astype(np.int32)
+            low = np.where(hit, low >> b, low)
+        return np.where(m == 0, -1, idx).astype(np.int32)
+
+    def matches_spans_packed(self, data, offsets, span_offsets, start, end, stream=None, out=None):
+        """needle_set_matches_spans_packed_dev (device tensors): which members match each span of a CSR span list over packed rows ->
+        an int32 device tensor of masks indexed like `start` (bit i: matches() of patterns[i] on row[start:end]); entries below
+        span_offsets[0] are untouched.  span_offsets int64[n_rows + 1], start / end int32 -- what Pattern.find_all_packed returns;
+        spans are clamped into their rows and need not be monotone or disjoint.  Stream-ordered, no host synchronisation."""
+        import torch
+        L = _lib.lib()
+        assert data.is_cuda and data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), \
+            "data: 1-D uint8 or (u)int16 code units on the device"
+        for name, t, dt in (("offsets", offsets, torch.int64), ("span_offsets", span_offsets, torch.int64), ("start", start, torch.int32),
+                            ("end", end, torch.int32)):
+            assert isinstance(t, torch.Tensor) and t.device == data.device and t.dtype == dt and t.dim() == 1 and t.is_contiguous(), \
+                "%s: 1-D %s on data's device" % (name, dt)
+        n = offsets.numel() - 1
+        assert n >= 0 and span_offsets.numel() == n + 1 and start.numel() == end.numel(), "span_offsets: n_rows + 1 entries; start / end alike"
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        with torch.cuda.device(data.device):
+            s = torch.cuda.current_stream(data.device).cuda_stream if stream is None else stream
+            if out is not None:  # a caller-owned result buffer (indexed like start)
+                assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= start.numel()
+                masks = out
+            else:
+                masks = torch.empty(start.numel(), dtype=torch.int32, device=data.device)
+            if start.numel() == 0:  # no span, nothing to write (and an empty tensor has no address to hand over)
+                return masks
+            _check(L.needle_set_matches_spans_packed_dev(self._h, ctypes.byref(v), span_offsets.data_ptr(), start.data_ptr(), end.data_ptr(),
+                                                         masks.data_ptr(), s))
+        return masks
+
+    def tag_matches_packed(self, pattern, data, offsets, stream=None):
+        """Every match of `pattern` in every packed row with the members that match it -> (match_offsets int64[n_rows + 1], start
+        int32[m], end int32[m], masks[m]).  Device tensors: pattern.find_all_packed, then matches_spans_packed on the same stream
+        (stream-ordered apart from the total that find_all_packed reads back); masks int32.  numpy data + offsets:
+        needle_set_tag_matches_packed_host; masks uint32."""
+        L = _lib.lib()
+        if isinstance(data, np.ndarray) or not (type(data).__module__.startswith("torch") and data.is_cuda):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.int16:
+                data = data.view(np.uint16)
+            assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            v = _lib.PackedView()
+            v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+            out = np.zeros(n + 1, dtype=np.uint64)
+            capacity = max(1024, 2 * n)
+            while True:  # (first with a guessed capacity, then with the exact total)
+                st = np.empty(capacity, dtype=np.int32)
+                en = np.empty(capacity, dtype=np.int32)
+                masks = np.zeros(capacity, dtype=np.uint32)
+                total = ctypes.c_uint64(0)
+                _check(L.needle_set_tag_matches_packed_host(self._h, pattern._h, ctypes.byref(v), out.ctypes.data, st.ctypes.data, en.ctypes.data,
+                                                            masks.ctypes.data, capacity, ctypes.byref(total)))
+                if total.value <= capacity:
+                    return out.astype(np.int64), st[:total.value], en[:total.value], masks[:total.value]
+                capacity = int(total.value)
+        off, st, en = pattern.find_all_packed(data, offsets, stream)
+        return off, st, en, self.matches_spans_packed(data, offsets, off, st, en, stream)
+
+    def find_all_tagged_strings(self, pattern, strings):
+        """Every match of `pattern` in every str (UTF-16 code units) with its member mask -> per string a list of (start, end, mask)
+        (pack_strings + the host entry)."""
+        data, offsets = pack_strings(strings)
+        off, st, en, masks = self.tag_matches_packed(pattern, data, offsets)
+        return [list(zip(st[off[i]:off[i + 1]].tolist(), en[off[i]:off[i + 1]].tolist(), masks[off[i]:off[i + 1]].tolist()))
+                for i in range(len(strings))]
 
     def info(self, op="contained_in", char_width=1):
         """The groups of one op and char width (host-side: needs no GPU): {"n_patterns", "n_groups", "groups": [{"first_pattern",

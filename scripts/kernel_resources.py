@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPRs / scratch of every instantiation of the tiled scan kernel, of the per-lane and the lock-step find-all kernels of fixed-stride
-rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel
-and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
+rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel,
+of the pattern-set kernel of span lists (needle_set_spans.h) and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
 (needle_replace.hip: 4 waves per workgroup, static LDS)
 (cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
@@ -19,7 +19,7 @@ for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", 
            "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2", "needle_packed_next1",
            "needle_packed_next2", "needle_packed_forms1", "needle_packed_forms2",
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
-           "needle_packed_set1", "needle_packed_set2",
+           "needle_packed_set1", "needle_packed_set2", "needle_set_spans1", "needle_set_spans2",
            "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2",
            "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace"):
     out = os.path.join(tmp, tu + ".s")
@@ -83,6 +83,12 @@ for k, sc, v in sorted(rows):
     m = re.search(r"packed_set_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d+)E", k)
     if m:
         print("%4d %4d  %-11s cw%s %-8s window %5d B" % (sc, v, names[m.group(1)], m.group(2), modes[m.group(3)], 64 * int(m.group(4))))
+# the pattern-set kernel of span lists (needle_set_spans.h): LDS = program + 1040 bytes of offsets per wave, sized at launch
+print("pattern-set span kernels (needle_set_spans.h): scratch bytes / VGPRs / kernel / LDS offsets per wave")
+for k, sc, v in sorted(rows):
+    m = re.search(r"set_spans_kernelILi(\d)ELi(\d)E", k)
+    if m:
+        print("%4d %4d  span masks  cw%s %-8s offsets %5d B" % (sc, v, m.group(1), modes[m.group(2)], 2 * 65 * 8))
 # the n-gram filter kernels (needle_ngram_kernel.h): LDS = program + bitmaps + per wave the queues and slots (packed rows: + the row starts)
 names_ng = dict(names, **{"3": "find-all"})
 for title, rx in (("n-gram filter kernels, fixed-stride rows (needle_ngram.hip): scratch bytes / VGPRs / kernel", r"ngram_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d)ELb(\d)ELb(\d)E"),
