@@ -370,6 +370,54 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         return result;
     }
 
+    /** The haystacks' bytes back to back; offsets[i] is where haystack i begins. */
+    private static byte[] flattenBytes(byte[][] haystacks, long[] offsets) {
+        for (int i = 0; i < haystacks.length; i++) {
+            offsets[i + 1] = offsets[i] + haystacks[i].length;
+        }
+        if (offsets[haystacks.length] > Integer.MAX_VALUE - 8) {
+            throw new IllegalArgumentException("the haystacks do not fit a byte[]: " + offsets[haystacks.length] + " bytes");
+        }
+        byte[] data = new byte[(int) offsets[haystacks.length]];
+        for (int i = 0; i < haystacks.length; i++) {
+            System.arraycopy(haystacks[i], 0, data, (int) offsets[i], haystacks[i].length);
+        }
+        return data;
+    }
+
+    /**
+     * Every non-overlapping match of every haystack of UTF-8 bytes, the pattern seeing what {@code new String(bytes, UTF_8)} gives
+     * (ill-formed input: one U+FFFD per maximal ill-formed subpart).  The bytes are decoded on the device; start / end of the result
+     * are BYTE offsets into the haystack, so a caller can cut or splice its original bytes
+     * (needle_find_all_csr_utf8_packed_host: a counting call sizes the result, a second call files it).
+     */
+    public Matches findAllUtf8(byte[][] haystacks) {
+        long[] offsets = new long[haystacks.length + 1];
+        byte[] data = flattenBytes(haystacks, offsets);
+        long[] matchOffsets = new long[haystacks.length + 1];
+        long[] total = new long[1];
+        check(Native.findAllUtf8PackedHost(handle, data, offsets, matchOffsets, null, null, total, null), null);
+        int[] start = new int[(int) total[0]];
+        int[] end = new int[(int) total[0]];
+        if (total[0] > 0) {
+            check(Native.findAllUtf8PackedHost(handle, data, offsets, matchOffsets, start, end, total, null), null);
+        }
+        return new Matches(matchOffsets, start, end);
+    }
+
+    /** containedIn() of every haystack of UTF-8 bytes, decoded on the device (needle_contained_in_utf8_packed_host). */
+    public boolean[] containedInUtf8(byte[][] haystacks) {
+        long[] offsets = new long[haystacks.length + 1];
+        byte[] data = flattenBytes(haystacks, offsets);
+        long[] bitmap = new long[(haystacks.length + 63) / 64];
+        check(Native.containedInUtf8PackedHost(handle, data, offsets, bitmap, null), null);
+        boolean[] result = new boolean[haystacks.length];
+        for (int i = 0; i < haystacks.length; i++) {
+            result[i] = ((bitmap[i >> 6] >>> (i & 63)) & 1L) != 0;
+        }
+        return result;
+    }
+
     /** The native pattern (GpuPatternSet copies its tables at creation). */
     long handle() {
         return handle;

@@ -58,6 +58,15 @@ final class Native {
     static native int findAllPackedHost(long handle, char[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end, long[] total);
 
     /**
+     * needle_find_all_csr_utf8_packed_host / needle_contained_in_utf8_packed_host: packed haystacks of UTF-8 bytes (data byte[] back to
+     * back + offsets[n + 1]), decoded on the device as {@code new String(bytes, UTF_8)} decodes them.  start / end are BYTE offsets into
+     * the haystack; malformed long[(n + 63) / 64] (may be null): the haystacks that hold ill-formed UTF-8.
+     */
+    static native int findAllUtf8PackedHost(long handle, byte[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end, long[] total, long[] malformed);
+
+    static native int containedInUtf8PackedHost(long handle, byte[] data, long[] offsets, long[] bitmap, long[] malformed);
+
+    /**
      * needle_replace_all_packed_host: every non-overlapping match of every packed haystack (data + offsets as packedHost) replaced by the
      * literal replacement (UTF-16 code units, at most 4096; empty: the matches are deleted).  outOffsets long[n + 1] and total long[1]
      * are always filled; out char[capacity] (null: size only) holds the result text when total[0] <= capacity.

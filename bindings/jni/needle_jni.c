@@ -357,6 +357,66 @@ NATIVE(jint, findAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data,
     return rc;
 }
 
+/* needle_find_all_csr_utf8_packed_host: data byte[] (the rows' UTF-8 bytes back to back) + offsets long[n + 1]; matchOffsets long[n + 1];
+ * start / end int[capacity] (may be null: count only), BYTE offsets into the row; total long[1]; malformed long[(n + 63) / 64] or null. */
+NATIVE(jint, findAllUtf8PackedHost)(JNIEnv *env, jclass c, jlong h, jbyteArray data, jlongArray offsets, jlongArray matchOffsets, jintArray start, jintArray end, jlongArray total, jlongArray malformed) {
+    if (!data || !offsets || !matchOffsets || !total) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, matchOffsets) < n1 || (*env)->GetArrayLength(env, total) < 1) return NEEDLE_ERR_INVALID;
+    if (malformed && (*env)->GetArrayLength(env, malformed) < (n1 - 1 + 63) / 64) return NEEDLE_ERR_INVALID;
+    jsize cap = start ? (*env)->GetArrayLength(env, start) : 0;
+    if (end && (*env)->GetArrayLength(env, end) < cap) cap = (*env)->GetArrayLength(env, end);
+    if (!end) cap = 0;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jbyte *d = (*env)->GetByteArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong *mo = (*env)->GetLongArrayElements(env, matchOffsets, NULL);
+    jint *st = cap ? (*env)->GetIntArrayElements(env, start, NULL) : NULL;
+    jint *en = cap ? (*env)->GetIntArrayElements(env, end, NULL) : NULL;
+    jlong *ml = malformed ? (*env)->GetLongArrayElements(env, malformed, NULL) : NULL;
+    v.data = d;
+    v.char_width = 1;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    uint64_t t = 0;
+    int rc = needle_find_all_csr_utf8_packed_host((const needle_pattern *)(intptr_t)h, &v, (uint64_t *)mo, (int32_t *)st, (int32_t *)en, (uint64_t)cap, &t,
+                                                  (uint64_t *)ml);
+    jlong jt = (jlong)t;
+    (*env)->SetLongArrayRegion(env, total, 0, 1, &jt);
+    (*env)->ReleaseByteArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, matchOffsets, mo, 0);
+    if (st) (*env)->ReleaseIntArrayElements(env, start, st, 0);
+    if (en) (*env)->ReleaseIntArrayElements(env, end, en, 0);
+    if (ml) (*env)->ReleaseLongArrayElements(env, malformed, ml, 0);
+    return rc;
+}
+
+/* needle_contained_in_utf8_packed_host: data + offsets as findAllUtf8PackedHost; bitmap long[(n + 63) / 64]; malformed the same, or null. */
+NATIVE(jint, containedInUtf8PackedHost)(JNIEnv *env, jclass c, jlong h, jbyteArray data, jlongArray offsets, jlongArray bitmap, jlongArray malformed) {
+    if (!data || !offsets || !bitmap) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, bitmap) < (n1 - 1 + 63) / 64) return NEEDLE_ERR_INVALID;
+    if (malformed && (*env)->GetArrayLength(env, malformed) < (n1 - 1 + 63) / 64) return NEEDLE_ERR_INVALID;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jbyte *d = (*env)->GetByteArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong *bm = (*env)->GetLongArrayElements(env, bitmap, NULL);
+    jlong *ml = malformed ? (*env)->GetLongArrayElements(env, malformed, NULL) : NULL;
+    v.data = d;
+    v.char_width = 1;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    int rc = needle_contained_in_utf8_packed_host((const needle_pattern *)(intptr_t)h, &v, (uint64_t *)bm, (uint64_t *)ml);
+    (*env)->ReleaseByteArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, bitmap, bm, 0);
+    if (ml) (*env)->ReleaseLongArrayElements(env, malformed, ml, 0);
+    return rc;
+}
+
 /* needle_replace_all_packed_host: data + offsets as packedHost; replacement char[] (may be empty, not null); outOffsets long[n + 1];
  * out char[capacity] (may be null: size only); total long[1]. */
 NATIVE(jint, replaceAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data, jlongArray offsets, jcharArray replacement, jlongArray outOffsets, jcharArray out, jlongArray total) {

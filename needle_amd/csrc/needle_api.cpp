@@ -1550,6 +1550,77 @@ int needle_replace_all_fill_packed_dev(const needle_packed_view *v, const uint64
     return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_all_fill_packed_dev");
 }
 
+// The UTF-8 front door (needle_utf8.hip): pure functions of the text (and a position list) -- no pattern, no route.  The checks all
+// three entries share, then the kernels' arguments and the device's CU count (n_rows == 0: not reached).
+static int utf8_view_check(const needle_packed_view *v) {
+    if (!v) return fail(NEEDLE_ERR_INVALID, "packed view is NULL");
+    if (v->char_width != 1) return fail(NEEDLE_ERR_INVALID, "UTF-8 rows are a packed view of char_width 1");
+    if (!v->offsets) return fail(NEEDLE_ERR_INVALID, "offsets is NULL");
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    return NEEDLE_OK;
+}
+static int utf8_args(const needle_packed_view *v, Utf8Args *a, int *cus) {
+    memset(a, 0, sizeof(*a));
+    a->data = (const uint8_t *)v->data;
+    a->in_off = v->offsets;
+    a->n_rows = v->n_rows;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return NEEDLE_OK;
+}
+
+int needle_utf16_lengths_from_utf8_packed_dev(const needle_packed_view *v, uint64_t *d_out_lengths, uint64_t *d_non_ascii, uint64_t *d_malformed,
+                                              void *stream_) {
+    int rc = utf8_view_check(v);
+    if (rc) return rc;
+    if (!d_out_lengths) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    Utf8Args a;
+    int cus = 0;
+    if ((rc = utf8_args(v, &a, &cus))) return rc;
+    a.out_len = d_out_lengths;
+    a.non_ascii = d_non_ascii;
+    a.malformed = d_malformed;
+    HIP_TRY(launch_utf8_lengths(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+int needle_utf16_from_utf8_packed_dev(const needle_packed_view *v, const uint64_t *d_out_offsets, uint16_t *d_out_data, void *stream_) {
+    int rc = utf8_view_check(v);
+    if (rc) return rc;
+    if (!d_out_offsets || !d_out_data) return fail(NEEDLE_ERR_INVALID, "output offsets / buffer is NULL");
+    if (((uintptr_t)d_out_data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "output data must be 4-byte aligned");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    Utf8Args a;
+    int cus = 0;
+    if ((rc = utf8_args(v, &a, &cus))) return rc;
+    a.out_off = d_out_offsets;
+    a.out = d_out_data;
+    HIP_TRY(launch_utf8_fill(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+// (d_unit_pos / d_byte_pos may be NULL when the list is empty, which only the device knows: the kernel then dereferences neither)
+int needle_utf8_positions_packed_dev(const needle_packed_view *v, const uint64_t *d_list_offsets, const int32_t *d_unit_pos, int32_t *d_byte_pos,
+                                     void *stream_) {
+    int rc = utf8_view_check(v);
+    if (rc) return rc;
+    if (!d_list_offsets) return fail(NEEDLE_ERR_INVALID, "list offsets is NULL");
+    if ((d_unit_pos == nullptr) != (d_byte_pos == nullptr)) return fail(NEEDLE_ERR_INVALID, "unit positions / byte positions: one of them is NULL");
+    if (v->n_rows == 0 || !d_unit_pos) return NEEDLE_OK;
+    Utf8Args a;
+    int cus = 0;
+    if ((rc = utf8_args(v, &a, &cus))) return rc;
+    a.list_off = d_list_offsets;
+    a.unit_pos = d_unit_pos;
+    a.byte_pos = d_byte_pos;
+    HIP_TRY(launch_utf8_positions(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+uint32_t needle_utf8_window_bytes(void) { return utf8_window_bytes(); }
+
 int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t max_per_row, uint64_t *d_offsets,
                                          uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);

@@ -1,6 +1,7 @@
 // needle_csr_rows.h -- what the kernels that take a CSR list over the rows of a packed batch share (needle_replace.hip: the match list
-// that is spliced; needle_set_spans.h: the span list that is tagged): a wave owns a 64-row group, keeps the group's 65 list offsets and 65
-// row offsets in its LDS, and a lane finds the row of its list entry there and clamps the entry into that row.
+// that is spliced; needle_set_spans.h: the span list that is tagged; needle_utf8.hip: the position list that is mapped): a wave owns a
+// 64-row group, keeps the group's 65 list offsets and 65 row offsets in its LDS, and a lane finds the row of its list entry there and
+// clamps the entry into that row.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +26,13 @@ __device__ __forceinline__ void csr_group_offsets(const uint64_t *list_off, cons
         mo[64] = list_off[r2];
         ino[64] = row_off[r2];
     }
+}
+
+// ... the 65 row offsets alone (needle_utf8.hip: kernels without a list).
+__device__ __forceinline__ void csr_group_row_offsets(const uint64_t *row_off, uint64_t n_rows, uint64_t g0, int lane, uint64_t *ino) {
+    const uint64_t r = g0 + (uint64_t)lane < n_rows ? g0 + (uint64_t)lane : n_rows;
+    ino[lane] = row_off[r];
+    if (lane == 0) ino[64] = row_off[g0 + 64u < n_rows ? g0 + 64u : n_rows];
 }
 
 // The row (0 .. 63 within the group) of list entry m: the last r with mo[r] <= m.

@@ -179,6 +179,24 @@ struct SetSpansArgs {
 };
 constexpr uint32_t kSetSpansWaveLds = 2u * 65u * 8u; // a wave's 65 span offsets + 65 row offsets behind the program
 
+// The UTF-8 front door (needle_utf8.hip): lengths, fill and positions take one struct, each its own part of it.
+constexpr int kUtf8Waves = 4;              // waves per workgroup; a wave owns a 64-row group at a time
+constexpr uint32_t kUtf8WindowBytes = 1024; // the text a wave classifies per step: 64 lanes x one aligned 16-byte block
+
+struct Utf8Args {
+    const uint8_t *data;      // the rows' UTF-8 bytes (device, 4-byte aligned)
+    const uint64_t *in_off;   // n_rows + 1 row offsets, in bytes
+    uint64_t n_rows;
+    uint64_t *out_len;        // lengths: n_rows unit counts
+    uint64_t *non_ascii;      // lengths: optional bitmaps of ceil(n_rows / 64) words
+    uint64_t *malformed;
+    const uint64_t *out_off;  // fill: n_rows + 1, in units
+    uint16_t *out;            // fill: the units (device, 4-byte aligned)
+    const uint64_t *list_off; // positions: n_rows + 1 offsets into unit_pos / byte_pos
+    const int32_t *unit_pos;
+    int32_t *byte_pos;
+};
+
 // Long rows of table-mode automata (needle_stripe.hip, "speculative stripes"): every stripe is first scanned as a row of
 // its own from the START state (the tiled kernel, all stripes in parallel); then each stripe whose true entry state
 // differs is re-walked next to the speculative run until the two states meet.

@@ -796,6 +796,114 @@ int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// UTF-8 packed host rows: transcoded on the device, byte positions back
+// ------------------------------------------------------------------------------------------------
+} // extern "C"
+
+// A packed HOST batch of UTF-8 rows (checked): chunks of whole 64-row groups (every chunk owns whole bitmap words) of at most
+// NEEDLE_HOST_CHUNK_BYTES of UTF-8 text + kUtf8RowBytes per row; ONE device buffer (utf8_chunk, as large as the largest chunk needs).  Per
+// chunk: upload, lengths, the units and both bitmaps downloaded (which synchronises), the malformed words into the caller's bitmap.  Then
+// run(dv8, dv16, out, r0, at): dv8 is the chunk as it lies; dv16 its UTF-16 form -- prefix sum here, fill -- or NULL when no row of the
+// chunk holds a byte >= 0x80: Latin-1 and UTF-8 agree on ASCII, the 8-bit entries serve and positions are the identity.
+template <class Run>
+static int for_utf8_chunks(const needle_packed_view *v, const char *who, uint64_t *malformed, Run &&run) {
+    const std::vector<RowRange> chunks = packed_chunks(v->offsets, v->n_rows, 1, kUtf8RowBytes, 64, host_chunk_bytes());
+    uint64_t all = 0;
+    for (const RowRange &c : chunks) {
+        Slab lay;
+        utf8_chunk(lay, c.second - c.first, v->offsets[c.second] - v->offsets[c.first]);
+        all = std::max(all, lay.total());
+    }
+    DevSlab dev;
+    HIP_TRY(dev.alloc(all));
+    std::vector<uint64_t> local, lens, words;
+    for (const RowRange &c : chunks) {
+        const uint64_t r0 = c.first, nr = c.second - c.first, nw = (nr + 63) / 64;
+        Slab lay;
+        const Utf8Chunk at = utf8_chunk(lay, nr, v->offsets[c.second] - v->offsets[r0]);
+        needle_packed_view dv8;
+        const hipError_t e = upload_packed_chunk(v, r0, c.second, dev.d + at.data, (uint64_t *)(dev.d + at.off), local, &dv8);
+        if (e != hipSuccess) return hip_fail(e, (std::string(who) + " upload").c_str());
+        const ChunkOut out{dev.d, who};
+        int rc = needle_utf16_lengths_from_utf8_packed_dev(&dv8, (uint64_t *)(dev.d + at.len), (uint64_t *)(dev.d + at.non_ascii),
+                                                           (uint64_t *)(dev.d + at.malformed), nullptr);
+        words.resize(nw);
+        if (rc || (malformed && (rc = out.download(malformed + r0 / 64, at.malformed, nw * 8))) || (rc = out.download(words.data(), at.non_ascii, nw * 8)))
+            return rc;
+        bool ascii = true;
+        for (uint64_t w : words) ascii = ascii && w == 0;
+        needle_packed_view dv16{dev.d + at.u16, 2, nr, (const uint64_t *)(dev.d + at.uoff)};
+        if (!ascii) {
+            lens.resize(nr + 1);
+            if ((rc = out.download(lens.data() + 1, at.len, nr * 8))) return rc;
+            lens[0] = 0;
+            for (uint64_t r = 1; r <= nr; ++r) lens[r] += lens[r - 1];
+            HIP_TRY(hipMemcpy(dev.d + at.uoff, lens.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
+            if ((rc = needle_utf16_from_utf8_packed_dev(&dv8, dv16.offsets, (uint16_t *)(dev.d + at.u16), nullptr))) return rc;
+        }
+        if ((rc = run(dv8, ascii ? nullptr : &dv16, out, r0, at))) return rc;
+    }
+    return NEEDLE_OK;
+}
+
+static int check_utf8_host(const needle_pattern *p, const needle_packed_view *v) {
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    if (!v) return fail(NEEDLE_ERR_INVALID, "packed view is NULL");
+    if (v->char_width != 1) return fail(NEEDLE_ERR_INVALID, "UTF-8 rows are a packed view of char_width 1");
+    if (!v->offsets) return fail(NEEDLE_ERR_INVALID, "offsets is NULL");
+    return NEEDLE_OK;
+}
+
+extern "C" {
+
+int needle_contained_in_utf8_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *bitmap, uint64_t *malformed) {
+    int rc = check_utf8_host(p, v);
+    if (rc) return rc;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if (!bitmap) return fail(NEEDLE_ERR_INVALID, "bitmap is NULL");
+    if ((rc = check_packed_rows(v, 0x7FFFFFFFull, "rows of at most 2^31 - 1 bytes"))) return rc;
+    return for_utf8_chunks(v, "contained_in_utf8_packed_host", malformed,
+                           [&](const needle_packed_view &dv8, const needle_packed_view *dv16, const ChunkOut &out, uint64_t r0, const Utf8Chunk &at) {
+                               const int rc = needle_contained_in_packed_dev(p, dv16 ? dv16 : &dv8, (uint64_t *)(out.d + at.bitmap), nullptr);
+                               return rc ? rc : out.download(bitmap + r0 / 64, at.bitmap, (dv8.n_rows + 63) / 64 * 8);
+                           });
+}
+
+// (per chunk, behind the transcoding: count pass, prefix sum here, fill pass in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of results
+// -- needle_find_all_csr_packed_host's -- with the positions kernel on start and on end, in place, before the sub-range's download)
+int needle_find_all_csr_utf8_packed_host(const needle_pattern *p, const needle_packed_view *v, uint64_t *offsets, int32_t *byte_start,
+                                         int32_t *byte_end, uint64_t capacity, uint64_t *total, uint64_t *malformed) {
+    const char *who = "find_all_csr_utf8_packed_host";
+    int rc = check_utf8_host(p, v);
+    if (rc) return rc;
+    if (!offsets || !total || (capacity && (!byte_start || !byte_end))) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    offsets[0] = 0;
+    *total = 0;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if ((rc = check_packed_rows(v, 0x7FFFFFFFull, "rows of at most 2^31 - 1 bytes"))) return rc;
+    std::vector<uint32_t> counts;
+    rc = for_utf8_chunks(v, who, malformed, [&](const needle_packed_view &dv8, const needle_packed_view *dv16, const ChunkOut &out, uint64_t r0, const Utf8Chunk &at) {
+        const needle_packed_view &tv = dv16 ? *dv16 : dv8; // the text the pattern scans
+        const uint64_t r1 = r0 + dv8.n_rows;
+        int rc = needle_count_matches_packed_dev(p, &tv, (uint32_t *)(out.d + at.cnt), nullptr);
+        if (rc || (rc = csr_offsets(out, at.cnt, r0, dv8.n_rows, counts, offsets))) return rc;
+        if (offsets[r1] == offsets[r0] || offsets[r1] > capacity) return (int)NEEDLE_OK;
+        return csr_fill_pass(who, offsets, r0, r1, out.d + at.csr, byte_start, byte_end,
+                             [&](uint64_t a, uint64_t sn, const uint64_t *d_csr, int32_t *d_s, int32_t *d_e, int *more) {
+                                 needle_packed_view sv = tv, s8 = dv8;
+                                 sv.offsets = tv.offsets + (a - r0), s8.offsets = dv8.offsets + (a - r0);
+                                 sv.n_rows = s8.n_rows = sn;
+                                 int rc = needle_find_all_csr_packed_dev(p, &sv, d_csr, d_s, d_e, more, nullptr);
+                                 if (rc || !dv16) return rc;
+                                 if ((rc = needle_utf8_positions_packed_dev(&s8, d_csr, d_s, d_s, nullptr))) return rc;
+                                 return needle_utf8_positions_packed_dev(&s8, d_csr, d_e, d_e, nullptr);
+                             });
+    });
+    if (rc == NEEDLE_OK) *total = offsets[v->n_rows];
+    return rc;
+}
+
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------

@@ -73,4 +73,28 @@ struct Slab {
     uint64_t total() const { return end; }
 };
 
+// One chunk of a UTF-8 packed host batch on the device (needle_*_utf8_packed_host): the text | its nr + 1 row offsets | the units of every
+// row | the nr + 1 unit offsets | the non-ASCII and malformed bitmaps | the results -- containedIn's bitmap, or find-all's counts and its
+// fill pass's offsets -- | the UTF-16 text.  units(row) <= bytes(row) (NEEDLE_UTF8_MAX_EXPANSION), so the UTF-16 form never needs more
+// than 2 bytes per byte of text: the chunk reserves text + 2 * text + the lists, whatever the rows hold.
+struct Utf8Chunk {
+    uint64_t data, off, len, uoff, non_ascii, malformed, bitmap, cnt, csr, u16;
+};
+constexpr uint64_t kUtf8RowBytes = 8 + 8 + 8 + 4 + 8 + 1; // what a row costs beside its text: offsets, units, unit offsets, count, csr, bitmaps
+inline Utf8Chunk utf8_chunk(Slab &lay, uint64_t nr, uint64_t text_bytes) {
+    const uint64_t words = (nr + 63) / 64 * 8;
+    Utf8Chunk c;
+    c.data = lay.add(std::max<uint64_t>(text_bytes, 4));
+    c.off = lay.add((nr + 1) * 8);
+    c.len = lay.add(nr * 8);
+    c.uoff = lay.add((nr + 1) * 8);
+    c.non_ascii = lay.add(words);
+    c.malformed = lay.add(words);
+    c.bitmap = lay.add(words);
+    c.cnt = lay.add(nr * 4);
+    c.csr = lay.add((nr + 1) * 8);
+    c.u16 = lay.add(std::max<uint64_t>(2 * text_bytes, 4));
+    return c;
+}
+
 } // namespace needle

@@ -75,6 +75,11 @@ hipError_t launch_ngram_packed_find_all(const ScanArgs &a, const uint64_t *row_o
 hipError_t launch_replace_put(const void *repl_host, uint32_t bytes, uint8_t *d_repl, hipStream_t stream);
 hipError_t launch_replace_lengths(const ReplaceArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_replace_fill(const ReplaceArgs &a, int n_cus, hipStream_t stream);
+// needle_utf8.hip: UTF-8 packed rows -> UTF-16 packed rows (lengths, fill), unit positions -> byte offsets; the text a wave takes per step
+hipError_t launch_utf8_lengths(const Utf8Args &a, int n_cus, hipStream_t stream);
+hipError_t launch_utf8_fill(const Utf8Args &a, int n_cus, hipStream_t stream);
+hipError_t launch_utf8_positions(const Utf8Args &a, int n_cus, hipStream_t stream);
+uint32_t utf8_window_bytes();
 // needle_lower.cpp (NEEDLE_PREFILTER)
 int ngram_level();
 

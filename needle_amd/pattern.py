@@ -1066,11 +1066,13 @@ class Pattern:
                 out_off[1:] += torch.cumsum(lens, 0)
             total = int(out_off[-1].item())
             if out is None:
-                out = torch.empty(total + 4, dtype=data.dtype, device=dv)[:total]  # (never an empty allocation: its pointer would be NULL)
+                room = torch.empty(total + 4, dtype=data.dtype, device=dv)  # (never an empty allocation: its pointer would be NULL)
+                out = room[:total]
             else:
                 assert out.device == dv and out.dtype == data.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= total
+                room = out
             _check(L.needle_replace_all_fill_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, r.ctypes.data if r.size else None, r.size,
-                                                        out_off.data_ptr(), out.data_ptr(), s))
+                                                        out_off.data_ptr(), room.data_ptr(), s))  # (an empty view's pointer is NULL too: a result of no units)
         return out, out_off
 
     def replace_all_packed(self, data, offsets, repl, stream=None, out=None, out_start=0):
@@ -1134,6 +1136,168 @@ class Pattern:
         data, offsets = pack_strings(strings)
         text, off = self.replace_all_packed(data, offsets, repl)
         return [text[off[i]:off[i + 1]].tobytes().decode("utf-16-le", "surrogatepass") for i in range(len(strings))]
+
+    # ---- UTF-8 packed rows: transcoded on the device, byte positions back (needle_utf16_*_from_utf8_packed_dev,
+    # needle_utf8_positions_packed_dev, needle_*_utf8_packed_host)
+    @staticmethod
+    def _utf8_dev(data, offsets):
+        """numpy UTF-8 bytes + offsets on the device (padded to whole 4 bytes) -> (data, offsets, True); device tensors as they are."""
+        import torch
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            data = torch.from_numpy(np.concatenate([data, np.zeros(4 + (-data.size) % 4, np.uint8)])).to("cuda")
+            return data, torch.from_numpy(np.ascontiguousarray(offsets).astype(np.int64)).to("cuda"), True
+        assert data.is_cuda and data.dim() == 1 and data.is_contiguous() and data.dtype == torch.uint8, "data: 1-D uint8 UTF-8 bytes"
+        assert isinstance(offsets, torch.Tensor) and offsets.device == data.device and offsets.dtype == torch.int64 and offsets.dim() == 1 \
+            and offsets.is_contiguous() and offsets.numel() >= 1, "offsets: 1-D int64, n + 1 entries, on data's device"
+        return data, offsets, False
+
+    @staticmethod
+    def utf16_from_utf8_packed(data, offsets, stream=None, out=None, out_start=0):
+        """UTF-8 packed rows (1-D uint8 bytes, int64 offsets[n + 1]; device tensors) -> (units int16, unit_offsets int64[n + 1],
+        non_ascii_words int64, malformed_words int64): the rows as bytes.decode("utf-8", "replace") / new String(bytes, UTF_8) gives them,
+        a packed batch of char width 2 for every *_packed method.  needle_utf16_lengths_from_utf8_packed_dev, torch cumsum,
+        needle_utf16_from_utf8_packed_dev on one stream, as splice_packed; the one host read is the total.  out / out_start: a
+        caller-owned int16 tensor, the result starting at its unit out_start (unit_offsets are positions in it; units outside
+        [unit_offsets[0], unit_offsets[n]) are left as they are).  numpy inputs are uploaded and the results brought back."""
+        import torch
+        L = _lib.lib()
+        data, offsets, host = Pattern._utf8_dev(data, offsets)
+        n, dv = offsets.numel() - 1, data.device
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), 1, n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            s = one.cuda_stream
+            words = (n + 63) // 64
+            room = torch.empty(n + 2 * words + 1, dtype=torch.int64, device=dv)  # (never an empty allocation: its pointer, and an empty view's, is NULL)
+            lens, na, mal = room[:n], room[n:n + words], room[n + words:n + 2 * words]
+            _check(L.needle_utf16_lengths_from_utf8_packed_dev(ctypes.byref(v), room.data_ptr(), room.data_ptr() + 8 * n, room.data_ptr() + 8 * (n + words), s))
+            uoff = torch.full((n + 1,), int(out_start), dtype=torch.int64, device=dv)
+            if n:
+                uoff[1:] += torch.cumsum(lens, 0)
+            total = int(uoff[-1].item())
+            if out is None:
+                text = torch.empty(total + 4, dtype=torch.int16, device=dv)
+                out = text[:total]
+            else:
+                assert out.device == dv and out.dtype == torch.int16 and out.dim() == 1 and out.is_contiguous() and out.numel() >= total
+                text = out
+            _check(L.needle_utf16_from_utf8_packed_dev(ctypes.byref(v), uoff.data_ptr(), text.data_ptr(), s))
+        if host:
+            return out.cpu().numpy().view(np.uint16), uoff.cpu().numpy(), na.cpu().numpy().view(np.uint64), mal.cpu().numpy().view(np.uint64)
+        return out, uoff, na, mal
+
+    @staticmethod
+    def utf8_positions_packed(data, offsets, list_offsets, unit_pos, stream=None, out=None):
+        """Code-unit positions of the rows' UTF-16 form -> byte offsets into the UTF-8 rows (needle_utf8_positions_packed_dev): a CSR list
+        over the rows (list_offsets int64[n + 1], unit_pos int32) -> byte_pos int32, indexed like unit_pos.  The second unit of a surrogate
+        pair maps to the start of its sequence, positions behind the row's end to its length, negative ones to -1.  out: a caller-owned
+        int32 tensor (entries outside [list_offsets[0], list_offsets[n]) are left as they are).  numpy inputs are uploaded."""
+        import torch
+        L = _lib.lib()
+        data, offsets, host = Pattern._utf8_dev(data, offsets)
+        dv, n = data.device, offsets.numel() - 1
+        if host:
+            list_offsets = torch.from_numpy(np.ascontiguousarray(list_offsets).astype(np.int64)).to(dv)
+            unit_pos = torch.from_numpy(np.ascontiguousarray(unit_pos).astype(np.int32)).to(dv)
+        for t, dt, what in ((list_offsets, torch.int64, "list_offsets"), (unit_pos, torch.int32, "unit_pos")):
+            assert isinstance(t, torch.Tensor) and t.device == dv and t.dtype == dt and t.dim() == 1 and t.is_contiguous(), what
+        assert list_offsets.numel() == n + 1
+        if out is None:
+            out = torch.empty(unit_pos.numel(), dtype=torch.int32, device=dv)
+        else:
+            assert out.device == dv and out.dtype == torch.int32 and out.dim() == 1 and out.is_contiguous() and out.numel() >= unit_pos.numel()
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), 1, n, offsets.data_ptr()
+        with torch.cuda.device(dv):
+            s = torch.cuda.current_stream(dv).cuda_stream if stream is None else stream
+            some = unit_pos.numel() > 0
+            _check(L.needle_utf8_positions_packed_dev(ctypes.byref(v), list_offsets.data_ptr(), unit_pos.data_ptr() if some else None,
+                                                      out.data_ptr() if some else None, s))
+        return out.cpu().numpy() if host else out
+
+    def _scan_utf8_packed(self, op, data, offsets, stream):
+        import torch
+        data, offsets, host = Pattern._utf8_dev(data, offsets)
+        one = torch.cuda.current_stream(data.device) if stream is None else torch.cuda.ExternalStream(stream, device=data.device)
+        with torch.cuda.device(data.device), torch.cuda.stream(one):
+            units, uoff, _, _ = Pattern.utf16_from_utf8_packed(data, offsets, stream=one.cuda_stream)
+            words = self._run_packed_dev(op, units, uoff, one.cuda_stream, None)
+        return words.cpu().numpy().view(np.uint64) if host else words
+
+    def _utf8_host_view(self, data, offsets):
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, 1, offsets.size - 1, offsets.ctypes.data
+        return v, (data, offsets)
+
+    def contained_in_utf8_packed(self, data, offsets, stream=None, malformed=False):
+        """Bitmap words of containedIn() of every UTF-8 packed row, the pattern seeing the row's decoded text.  Device tensors:
+        utf16_from_utf8_packed, then contained_in_packed on the UTF-16 batch, on one stream.  numpy data + offsets:
+        needle_contained_in_utf8_packed_host; malformed=True -> (words, malformed_words: the rows that hold ill-formed UTF-8)."""
+        if not isinstance(data, np.ndarray):
+            assert not malformed, "malformed words: utf16_from_utf8_packed gives them on the device"
+            return self._scan_utf8_packed("contained_in", data, offsets, stream)
+        L = _lib.lib()
+        v, keep = self._utf8_host_view(data, offsets)
+        words = np.zeros((v.n_rows + 63) // 64, dtype=np.uint64)
+        mal = np.zeros_like(words)
+        _check(L.needle_contained_in_utf8_packed_host(self._h, ctypes.byref(v), words.ctypes.data, mal.ctypes.data))
+        return (words, mal) if malformed else words
+
+    def matches_utf8_packed(self, data, offsets, stream=None):
+        """Bitmap words of matches() of every UTF-8 packed row's decoded text (device chain; numpy inputs are uploaded)."""
+        return self._scan_utf8_packed("matches", data, offsets, stream)
+
+    def find_all_utf8_packed(self, data, offsets, stream=None):
+        """Every non-overlapping match of every UTF-8 packed row -> (match_offsets int64[n + 1], byte_start int32[m], byte_end int32[m]):
+        the matches find_all_packed files on the rows' decoded text, as BYTE offsets into the rows -- what splice_packed takes with the
+        original bytes.  Device tensors: utf16_from_utf8_packed, find_all_packed, utf8_positions_packed on start and on end, one
+        stream.  numpy data + offsets: needle_find_all_csr_utf8_packed_host."""
+        if isinstance(data, np.ndarray):
+            L = _lib.lib()
+            v, keep = self._utf8_host_view(data, offsets)
+            out = np.zeros(v.n_rows + 1, dtype=np.uint64)
+            capacity = max(1024, 2 * v.n_rows)
+            while True:  # (first with a guessed capacity, then with the exact total)
+                st = np.empty(capacity, dtype=np.int32)
+                en = np.empty(capacity, dtype=np.int32)
+                total = ctypes.c_uint64(0)
+                _check(L.needle_find_all_csr_utf8_packed_host(self._h, ctypes.byref(v), out.ctypes.data, st.ctypes.data, en.ctypes.data, capacity,
+                                                              ctypes.byref(total), None))
+                if total.value <= capacity:
+                    return out.astype(np.int64), st[:total.value], en[:total.value]
+                capacity = int(total.value)
+        import torch
+        data, offsets, _ = Pattern._utf8_dev(data, offsets)
+        one = torch.cuda.current_stream(data.device) if stream is None else torch.cuda.ExternalStream(stream, device=data.device)
+        with torch.cuda.device(data.device), torch.cuda.stream(one):
+            s = one.cuda_stream
+            units, uoff, _, _ = Pattern.utf16_from_utf8_packed(data, offsets, stream=s)
+            moff, st, en = self.find_all_packed(units, uoff, stream=s)
+            bs = Pattern.utf8_positions_packed(data, offsets, moff, st, stream=s)
+            be = Pattern.utf8_positions_packed(data, offsets, moff, en, stream=s)
+        return moff, bs, be
+
+    def find_all_bytes(self, rows):
+        """Every non-overlapping match of every UTF-8 `bytes` row -> list of [(byte_start, byte_end), ...] per row: pack_bytes +
+        find_all_utf8_packed, the counterpart of find_all_strings for text that is not a str."""
+        data, offsets = pack_bytes(rows)
+        off, st, en = self.find_all_utf8_packed(data, offsets)
+        return [list(zip(st[off[i]:off[i + 1]].tolist(), en[off[i]:off[i + 1]].tolist())) for i in range(len(rows))]
+
+    def replace_all_bytes(self, rows, repl):
+        """Every match of every UTF-8 `bytes` row replaced by the bytes `repl` -> list[bytes]: find_all_utf8_packed on the device, then
+        splice_packed at char width 1 on the ORIGINAL bytes with the replacement's bytes -- no encoder back to UTF-8 is involved, and the
+        bytes of ill-formed input outside the matches come back untouched."""
+        data, offsets = pack_bytes(rows)
+        d, o, _ = Pattern._utf8_dev(data, offsets)
+        moff, bs, be = self.find_all_utf8_packed(d, o)
+        text, off = Pattern.splice_packed(d, o, moff, bs, be, np.frombuffer(bytes(repl), dtype=np.uint8))
+        text, off = text.cpu().numpy(), off.cpu().numpy()
+        return [text[off[i]:off[i + 1]].tobytes() for i in range(len(rows))]
 
     @staticmethod
     def rows_from_packed(data, offsets, row_stride=None, stream=None):
@@ -1365,6 +1529,14 @@ def pack_strings(strings):
         offsets[1:] = np.cumsum([u.size for u in units])
     data = np.concatenate(units) if units else np.zeros(0, dtype=np.uint16)
     return data.astype(np.uint16), offsets
+
+
+def pack_bytes(rows):
+    """list[bytes] (UTF-8, or whatever the rows hold) -> (uint8 bytes back to back, uint64 offsets[n + 1]): the layout of an Arrow string column."""
+    offsets = np.zeros(len(rows) + 1, dtype=np.uint64)
+    if rows:
+        offsets[1:] = np.cumsum([len(x) for x in rows])
+    return np.frombuffer(b"".join(bytes(x) for x in rows), dtype=np.uint8).copy(), offsets
 
 
 def unpack_bitmap(words, n_rows):
