@@ -100,6 +100,47 @@ public final class GpuPatternSet implements AutoCloseable {
     }
 
     /**
+     * A rule list in one call: every non-overlapping match of {@code pattern} (typically the union (r0)|(r1)|.. of this set's rules) in
+     * every haystack is replaced by {@code replacements[j]}, j the LOWEST pattern of this set that matches() the match's text as a
+     * whole -- the first rule of an ordered rule list -- and kept as it is when no pattern of the set does.  One replacement per pattern
+     * of the set, literal as in {@link GpuPattern#replaceAllStrings}, at most 4096 chars in all; an empty one deletes its rule's
+     * matches.  A sizing call, then the call that files the text (needle_set_replace_each_packed_host).
+     */
+    public String[] replaceEachStrings(GpuPattern pattern, String[] haystacks, String[] replacements) {
+        long[] offsets = new long[haystacks.length + 1];
+        for (int i = 0; i < haystacks.length; i++) {
+            offsets[i + 1] = offsets[i] + haystacks[i].length();
+        }
+        char[] data = new char[(int) offsets[haystacks.length]];
+        for (int i = 0; i < haystacks.length; i++) {
+            haystacks[i].getChars(0, haystacks[i].length(), data, (int) offsets[i]);
+        }
+        int[] replOffsets = new int[replacements.length + 1];
+        for (int i = 0; i < replacements.length; i++) {
+            replOffsets[i + 1] = replOffsets[i] + replacements[i].length();
+        }
+        char[] repl = new char[replOffsets[replacements.length]];
+        for (int i = 0; i < replacements.length; i++) {
+            replacements[i].getChars(0, replacements[i].length(), repl, replOffsets[i]);
+        }
+        long[] outOffsets = new long[haystacks.length + 1];
+        long[] total = new long[1];
+        GpuPattern.check(Native.setReplaceEachPackedHost(handle, pattern.handle(), data, offsets, repl, replOffsets, outOffsets, null, total), "(pattern set)");
+        if (total[0] > Integer.MAX_VALUE - 8) {
+            throw new IllegalArgumentException("the result does not fit a char[]: " + total[0] + " chars");
+        }
+        char[] out = new char[(int) total[0]];
+        if (total[0] > 0) {
+            GpuPattern.check(Native.setReplaceEachPackedHost(handle, pattern.handle(), data, offsets, repl, replOffsets, outOffsets, out, total), "(pattern set)");
+        }
+        String[] result = new String[haystacks.length];
+        for (int i = 0; i < haystacks.length; i++) {
+            result[i] = new String(out, (int) outOffsets[i], (int) (outOffsets[i + 1] - outOffsets[i]));
+        }
+        return result;
+    }
+
+    /**
      * needle_set_matches_spans_packed_dev for a host whose batch and match list are ALREADY in device memory: every argument but
      * charWidth and nRows is a device address (data 4-byte aligned; offsets and spanOffsets nRows + 1 uint64; start / end int32 relative
      * to the row, 0 only when there are no spans; masks uint32 indexed like start), stream a hipStream_t (0: the null stream).

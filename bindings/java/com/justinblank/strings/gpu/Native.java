@@ -100,6 +100,13 @@ final class Native {
     static native int setTagMatchesPackedHost(long set, long pattern, char[] data, long[] offsets, long[] matchOffsets, int[] start, int[] end,
                                               int[] masks, long[] total);
 
+    /**
+     * needle_set_replace_each_packed_host: replaceAllPackedHost with a replacement per pattern of the set -- replacements char[] back
+     * to back (may be empty, not null), replOffsets int[nPatterns + 1]; out char[capacity] (may be null: size only); total long[1].
+     */
+    static native int setReplaceEachPackedHost(long set, long pattern, char[] data, long[] offsets, char[] replacements, int[] replOffsets,
+                                               long[] outOffsets, char[] out, long[] total);
+
     /** needle_set_matches_spans_packed_dev: every long but nRows is a device address (stream: a hipStream_t). */
     static native int setMatchesSpansPackedDev(long set, long data, int charWidth, long nRows, long offsets, long spanOffsets, long start,
                                                long end, long masks, long stream);

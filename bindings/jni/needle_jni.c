@@ -558,6 +558,47 @@ NATIVE(jint, setTagMatchesPackedHost)(JNIEnv *env, jclass c, jlong s, jlong h, j
     return rc;
 }
 
+/* needle_set_replace_each_packed_host: data + offsets as packedHost; replacements char[] (may be empty, not null) located by
+ * replOffsets int[nPatterns + 1]; outOffsets long[n + 1]; out char[capacity] (may be null: size only); total long[1]. */
+NATIVE(jint, setReplaceEachPackedHost)(JNIEnv *env, jclass c, jlong s, jlong h, jcharArray data, jlongArray offsets, jcharArray replacements,
+                                       jintArray replOffsets, jlongArray outOffsets, jcharArray out, jlongArray total) {
+    if (!data || !offsets || !replacements || !replOffsets || !outOffsets || !total) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    const jsize k1 = (*env)->GetArrayLength(env, replOffsets);
+    if (n1 < 1 || k1 < 2 || (*env)->GetArrayLength(env, outOffsets) < n1 || (*env)->GetArrayLength(env, total) < 1) return NEEDLE_ERR_INVALID;
+    const jsize cap = out ? (*env)->GetArrayLength(env, out) : 0;
+    const jsize rn = (*env)->GetArrayLength(env, replacements);
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jint *ro = (*env)->GetIntArrayElements(env, replOffsets, NULL);
+    if (ro[0] != 0 || ro[k1 - 1] < 0 || ro[k1 - 1] > rn) { /* (the table must lie inside the array; the entry checks the rest) */
+        (*env)->ReleaseIntArrayElements(env, replOffsets, ro, JNI_ABORT);
+        return NEEDLE_ERR_INVALID;
+    }
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jchar *r = (*env)->GetCharArrayElements(env, replacements, NULL);
+    jlong *oo = (*env)->GetLongArrayElements(env, outOffsets, NULL);
+    jchar *text = cap ? (*env)->GetCharArrayElements(env, out, NULL) : NULL;
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    uint64_t t = 0;
+    int rc = needle_set_replace_each_packed_host((const needle_pattern_set *)(intptr_t)s, (const needle_pattern *)(intptr_t)h, &v,
+                                                 rn ? (const void *)r : NULL, (const uint32_t *)ro, (uint32_t)(k1 - 1), (uint64_t *)oo, text,
+                                                 (uint64_t)cap, &t);
+    jlong jt = (jlong)t;
+    (*env)->SetLongArrayRegion(env, total, 0, 1, &jt);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseCharArrayElements(env, replacements, r, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, replOffsets, ro, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, outOffsets, oo, 0);
+    if (text) (*env)->ReleaseCharArrayElements(env, out, text, 0);
+    return rc;
+}
+
 /* needle_set_matches_spans_packed_dev: device addresses as jlong. */
 NATIVE(jint, setMatchesSpansPackedDev)(JNIEnv *env, jclass c, jlong s, jlong data, jint charWidth, jlong nRows, jlong offsets, jlong spanOffsets,
                                        jlong start, jlong end, jlong masks, jlong stream) {

@@ -1550,6 +1550,97 @@ int needle_replace_all_fill_packed_dev(const needle_packed_view *v, const uint64
     return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_all_fill_packed_dev");
 }
 
+// The splice with a replacement per match (needle_replace_each.hip): the checks of replace_args, then the table's and the choices'.
+// `repl` is checked by the fill entry alone (the lengths entry has none).
+static int replace_each_args(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start, const int32_t *d_end,
+                             const void *d_choice, int choice_form, const uint32_t *repl_offsets, uint32_t n_repl, ReplaceEachArgs *a) {
+    ReplaceArgs plain;
+    int rc = replace_args(v, d_match_offsets, d_start, d_end, 0, &plain);
+    if (rc) return rc;
+    if (choice_form != NEEDLE_CHOICE_INDEX && choice_form != NEEDLE_CHOICE_LOWEST_BIT)
+        return fail(NEEDLE_ERR_INVALID, "choice_form is neither NEEDLE_CHOICE_INDEX nor NEEDLE_CHOICE_LOWEST_BIT");
+    if (!repl_offsets) return fail(NEEDLE_ERR_INVALID, "replacement offsets is NULL");
+    if (n_repl < 1 || n_repl > NEEDLE_REPLACE_MAX_CHOICES) return fail(NEEDLE_ERR_INVALID, "1 .. NEEDLE_REPLACE_MAX_CHOICES replacements");
+    if (repl_offsets[0] != 0) return fail(NEEDLE_ERR_INVALID, "replacement offsets must start at 0");
+    for (uint32_t i = 0; i < n_repl; ++i)
+        if (repl_offsets[i + 1] < repl_offsets[i]) return fail(NEEDLE_ERR_INVALID, "replacement offsets decrease");
+    if (repl_offsets[n_repl] > NEEDLE_REPLACE_MAX_UNITS)
+        return fail(NEEDLE_ERR_INVALID, "replacement table longer than NEEDLE_REPLACE_MAX_UNITS code units");
+    memset(a, 0, sizeof(*a));
+    a->data = plain.data;
+    a->in_off = plain.in_off;
+    a->n_rows = plain.n_rows;
+    a->cw = plain.cw;
+    a->n_repl = n_repl;
+    a->choice_form = (uint32_t)choice_form;
+    a->table_units = repl_offsets[n_repl];
+    a->match_off = d_match_offsets;
+    a->start = d_start;
+    a->end = d_end;
+    a->choice = (const uint32_t *)d_choice;
+    return NEEDLE_OK;
+}
+
+// The table on the device, in stream order: its offsets (kReplaceEachOffsetBytes, zeros behind n_repl + 1) and, with_units, its code
+// units behind them, through kernel arguments as the plain replacement goes (launch_replace_put): the caller's arrays are free on return.
+static hipError_t replace_each_table(const void *repl, const uint32_t *repl_offsets, uint32_t n_repl, uint32_t cw, bool with_units, uint8_t **d_table,
+                                     hipStream_t stream) {
+    const uint32_t unit_bytes = with_units ? repl_offsets[n_repl] * cw : 0u;
+    const uint32_t bytes = kReplaceEachOffsetBytes + ((unit_bytes + 15u) & ~15u);
+    std::vector<uint8_t> host(bytes, 0);
+    memcpy(host.data(), repl_offsets, (size_t)(n_repl + 1) * 4);
+    if (unit_bytes) memcpy(host.data() + kReplaceEachOffsetBytes, repl, unit_bytes);
+    hipError_t e = scratch_malloc((void **)d_table, bytes, stream);
+    if (e != hipSuccess) return e;
+    return launch_replace_put(host.data(), bytes, *d_table, stream);
+}
+
+int needle_replace_each_lengths_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start,
+                                           const int32_t *d_end, const void *d_choice, int choice_form, const uint32_t *repl_offsets,
+                                           uint32_t n_repl, uint64_t *d_out_lengths, void *stream_) {
+    ReplaceEachArgs a;
+    int rc = replace_each_args(v, d_match_offsets, d_start, d_end, d_choice, choice_form, repl_offsets, n_repl, &a);
+    if (rc) return rc;
+    if (!d_out_lengths) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    a.out_len = d_out_lengths;
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    uint8_t *d_table = nullptr;
+    hipError_t e = replace_each_table(nullptr, repl_offsets, n_repl, v->char_width, false, &d_table, stream);
+    a.table = d_table;
+    if (e == hipSuccess) e = launch_replace_each_lengths(a, cus, stream);
+    if (d_table) (void)scratch_free(d_table, stream);
+    return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_each_lengths_packed_dev");
+}
+
+int needle_replace_each_fill_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start,
+                                        const int32_t *d_end, const void *d_choice, int choice_form, const void *repl,
+                                        const uint32_t *repl_offsets, uint32_t n_repl, const uint64_t *d_out_offsets, void *d_out_data,
+                                        void *stream_) {
+    ReplaceEachArgs a;
+    int rc = replace_each_args(v, d_match_offsets, d_start, d_end, d_choice, choice_form, repl_offsets, n_repl, &a);
+    if (rc) return rc;
+    if (!d_out_offsets || !d_out_data) return fail(NEEDLE_ERR_INVALID, "output offsets / buffer is NULL");
+    if (((uintptr_t)d_out_data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "output data must be 4-byte aligned");
+    if (repl_offsets[n_repl] && !repl) return fail(NEEDLE_ERR_INVALID, "replacement table is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    a.out_off = d_out_offsets;
+    a.out = (uint8_t *)d_out_data;
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    uint8_t *d_table = nullptr;
+    hipError_t e = replace_each_table(repl, repl_offsets, n_repl, v->char_width, true, &d_table, stream);
+    a.table = d_table;
+    if (e == hipSuccess) e = launch_replace_each_fill(a, cus, stream);
+    if (d_table) (void)scratch_free(d_table, stream);
+    return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_each_fill_packed_dev");
+}
+
 // The UTF-8 front door (needle_utf8.hip): pure functions of the text (and a position list) -- no pattern, no route.  The checks all
 // three entries share, then the kernels' arguments and the device's CU count (n_rows == 0: not reached).
 static int utf8_view_check(const needle_packed_view *v) {
@@ -2389,6 +2480,7 @@ int needle::set_plan_usable(const needle_pattern_set *s, int op, int char_width)
     const std::string &why = s->refused[op][char_width - 1];
     return why.empty() ? NEEDLE_OK : fail(NEEDLE_ERR_UNSUPPORTED, why);
 }
+uint32_t needle::set_pattern_count(const needle_pattern_set *s) { return (uint32_t)s->members.size(); }
 
 // One group's program on the current device, built on first use and cached in the set (as get_program does for patterns).
 static int set_program(needle_pattern_set *s, int op, int cw, int group, const uint8_t **d_blob, int *n_cus) {

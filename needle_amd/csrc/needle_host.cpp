@@ -706,19 +706,18 @@ int needle_set_tag_matches_packed_host(const needle_pattern_set *s, const needle
     return find_all_csr_packed_host("set_tag_matches_packed_host", p, v, offsets, start, end, capacity, total, s, masks);
 }
 
+} // extern "C"
+
 // Replace every match of a packed HOST batch.  Per chunk of rows (36 bytes per row: offset, count, match offset, length, output offset):
 // upload, count pass, prefix sum here; then in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of matches: CSR fill, lengths, prefix sum
 // here into the caller's out_offsets; then, while the caller's buffer has room, in sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of
 // output text: splice and download.  The offsets handed to the device are rebased to each sub-range.
-int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_view *v, const void *repl, uint32_t repl_len, uint64_t *out_offsets,
-                                   void *out_data, uint64_t capacity, uint64_t *total) {
-    const char *who = "replace_all_packed_host";
-    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
-    int rc = check_packed(v);
-    if (rc) return rc;
-    if (!out_offsets || !total || (capacity && !out_data)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
-    if (repl_len > NEEDLE_REPLACE_MAX_UNITS) return fail(NEEDLE_ERR_INVALID, "replacement longer than NEEDLE_REPLACE_MAX_UNITS code units");
-    if (repl_len && !repl) return fail(NEEDLE_ERR_INVALID, "replacement is NULL");
+// set != NULL (needle_set_replace_each_packed_host): repl is a table of set's-pattern-count entries at repl_offsets; every match is tagged
+// by the set in the sub-range loop of the CSR fill, and the masks go straight into the each-entries (NEEDLE_CHOICE_LOWEST_BIT).
+static int replace_packed_host(const char *who, const needle_pattern *p, const needle_packed_view *v, const void *repl, uint32_t repl_len,
+                               const needle_pattern_set *set, const uint32_t *repl_offsets, uint32_t n_repl, uint64_t *out_offsets, void *out_data,
+                               uint64_t capacity, uint64_t *total) {
+    int rc = 0;
     out_offsets[0] = 0;
     *total = 0;
     if (v->n_rows == 0) return NEEDLE_OK;
@@ -746,11 +745,12 @@ int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_
             uint64_t biggest = 0;
             for (const RowRange &rg : ranges) biggest = std::max<uint64_t>(biggest, moff[rg.second] - moff[rg.first]);
             Slab lay;
-            const uint64_t o_s = lay.add(biggest * 4), o_e = lay.add(biggest * 4);
+            const uint64_t o_s = lay.add(biggest * 4), o_e = lay.add(biggest * 4), o_m = set ? lay.add(biggest * 4) : 0;
             DevSlab list;
             hipError_t e = list.alloc(lay.total());
             if (e != hipSuccess) return hip_fail(e, "replace_all_packed_host matches");
             int32_t *d_s = (int32_t *)(list.d + o_s), *d_e = (int32_t *)(list.d + o_e);
+            uint32_t *d_m = (uint32_t *)(list.d + o_m); // (each match's member mask: the choice)
             for (const RowRange &rg : ranges) {
                 const uint64_t a = rg.first, sn = rg.second - rg.first;
                 local.resize(sn + 1);
@@ -762,7 +762,10 @@ int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_
                 int more = 0;
                 if (local[sn] && (rc = needle_find_all_csr_packed_dev(p, &sv, d_moff, d_s, d_e, &more, nullptr))) return rc;
                 if (more) return fail(NEEDLE_ERR_DEVICE, "replace_all_packed_host: count pass and fill pass disagree");
-                if ((rc = needle_replace_all_lengths_packed_dev(&sv, d_moff, d_s, d_e, repl_len, d_len, nullptr))) return rc;
+                if (set && local[sn] && (rc = needle_set_matches_spans_packed_dev(set, &sv, d_moff, d_s, d_e, d_m, nullptr))) return rc;
+                rc = set ? needle_replace_each_lengths_packed_dev(&sv, d_moff, d_s, d_e, d_m, NEEDLE_CHOICE_LOWEST_BIT, repl_offsets, n_repl, d_len, nullptr)
+                         : needle_replace_all_lengths_packed_dev(&sv, d_moff, d_s, d_e, repl_len, d_len, nullptr);
+                if (rc) return rc;
                 lens.resize(sn);
                 if ((rc = out.download(lens.data(), o.len, sn * 8))) return rc;
                 uint64_t *oo = out_offsets + r0 + a;
@@ -785,7 +788,10 @@ int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_
                     needle_packed_view tv = dv;
                     tv.offsets = dv.offsets + x;
                     tv.n_rows = pn;
-                    if ((rc = needle_replace_all_fill_packed_dev(&tv, d_moff + (x - a), d_s, d_e, repl, repl_len, d_ooff, text.d, nullptr))) return rc;
+                    rc = set ? needle_replace_each_fill_packed_dev(&tv, d_moff + (x - a), d_s, d_e, d_m, NEEDLE_CHOICE_LOWEST_BIT, repl, repl_offsets, n_repl,
+                                                                   d_ooff, text.d, nullptr)
+                             : needle_replace_all_fill_packed_dev(&tv, d_moff + (x - a), d_s, d_e, repl, repl_len, d_ooff, text.d, nullptr);
+                    if (rc) return rc;
                     e = hipMemcpy((uint8_t *)out_data + out_offsets[pc.first] * cw, text.d, units * cw, hipMemcpyDeviceToHost);
                     if (e != hipSuccess) return hip_fail(e, "replace_all_packed_host download");
                 }
@@ -794,6 +800,40 @@ int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_
         });
     if (rc == NEEDLE_OK) *total = out_offsets[v->n_rows];
     return rc;
+}
+extern "C" {
+
+int needle_replace_all_packed_host(const needle_pattern *p, const needle_packed_view *v, const void *repl, uint32_t repl_len, uint64_t *out_offsets,
+                                   void *out_data, uint64_t capacity, uint64_t *total) {
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!out_offsets || !total || (capacity && !out_data)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (repl_len > NEEDLE_REPLACE_MAX_UNITS) return fail(NEEDLE_ERR_INVALID, "replacement longer than NEEDLE_REPLACE_MAX_UNITS code units");
+    if (repl_len && !repl) return fail(NEEDLE_ERR_INVALID, "replacement is NULL");
+    return replace_packed_host("replace_all_packed_host", p, v, repl, repl_len, nullptr, nullptr, 0, out_offsets, out_data, capacity, total);
+}
+
+// Replace each match of `p` by the replacement of the lowest member of `s` that matches it whole; a match no member matches is kept.
+int needle_set_replace_each_packed_host(const needle_pattern_set *s, const needle_pattern *p, const needle_packed_view *v, const void *repl,
+                                        const uint32_t *repl_offsets, uint32_t n_repl, uint64_t *out_offsets, void *out_data, uint64_t capacity,
+                                        uint64_t *total) {
+    if (!s) return fail(NEEDLE_ERR_INVALID, "pattern set is NULL");
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!out_offsets || !total || (capacity && !out_data)) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (!repl_offsets) return fail(NEEDLE_ERR_INVALID, "replacement offsets is NULL");
+    if (n_repl < 1 || n_repl > NEEDLE_REPLACE_MAX_CHOICES) return fail(NEEDLE_ERR_INVALID, "1 .. NEEDLE_REPLACE_MAX_CHOICES replacements");
+    if (repl_offsets[0] != 0) return fail(NEEDLE_ERR_INVALID, "replacement offsets must start at 0");
+    for (uint32_t i = 0; i < n_repl; ++i)
+        if (repl_offsets[i + 1] < repl_offsets[i]) return fail(NEEDLE_ERR_INVALID, "replacement offsets decrease");
+    if (repl_offsets[n_repl] > NEEDLE_REPLACE_MAX_UNITS)
+        return fail(NEEDLE_ERR_INVALID, "replacement table longer than NEEDLE_REPLACE_MAX_UNITS code units");
+    if (repl_offsets[n_repl] && !repl) return fail(NEEDLE_ERR_INVALID, "replacement table is NULL");
+    if (n_repl != set_pattern_count(s)) return fail(NEEDLE_ERR_INVALID, "one replacement per member of the set");
+    if (v->n_rows && (rc = set_plan_usable(s, OP_MATCHES, (int)v->char_width))) return rc;
+    return replace_packed_host("set_replace_each_packed_host", p, v, repl, 0, s, repl_offsets, n_repl, out_offsets, out_data, capacity, total);
 }
 
 // ------------------------------------------------------------------------------------------------

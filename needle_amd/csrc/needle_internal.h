@@ -27,6 +27,8 @@ int find_compact(const needle_pattern *p, const needle_batch_view *v, uint64_t *
 bool find_all_rounds_forced();
 // needle_api.cpp: NEEDLE_ERR_UNSUPPORTED where the set has no plan for this op (OP_MATCHES | OP_CONTAINED_IN) and char width (1 | 2)
 int set_plan_usable(const needle_pattern_set *s, int op, int char_width);
+// needle_api.cpp: the set's members (1 .. 32)
+uint32_t set_pattern_count(const needle_pattern_set *s);
 // needle_api.cpp: what the Matcher mirror reads of the pattern where the generated loops are skipped
 struct MatcherRoots {
     bool forwards_root_accepts, backwards_root_accepts;

@@ -9,6 +9,7 @@
 #include "needle_find_all.h"
 #include "needle_ngram.h"
 #include "needle_replace.h"
+#include "needle_replace_each.h"
 
 namespace needle {
 
@@ -75,6 +76,9 @@ hipError_t launch_ngram_packed_find_all(const ScanArgs &a, const uint64_t *row_o
 hipError_t launch_replace_put(const void *repl_host, uint32_t bytes, uint8_t *d_repl, hipStream_t stream);
 hipError_t launch_replace_lengths(const ReplaceArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_replace_fill(const ReplaceArgs &a, int n_cus, hipStream_t stream);
+// needle_replace_each.hip: the splice with a replacement per match out of a table (needle_replace_each_*_packed_dev)
+hipError_t launch_replace_each_lengths(const ReplaceEachArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_replace_each_fill(const ReplaceEachArgs &a, int n_cus, hipStream_t stream);
 // needle_utf8.hip: UTF-8 packed rows -> UTF-16 packed rows (lengths, fill), unit positions -> byte offsets; the text a wave takes per step
 hipError_t launch_utf8_lengths(const Utf8Args &a, int n_cus, hipStream_t stream);
 hipError_t launch_utf8_fill(const Utf8Args &a, int n_cus, hipStream_t stream);

@@ -1075,6 +1075,73 @@ class Pattern:
                                                         out_off.data_ptr(), room.data_ptr(), s))  # (an empty view's pointer is NULL too: a result of no units)
         return out, out_off
 
+    @staticmethod
+    def _repl_table(repls, char_width):
+        """A replacement table (a list of str or 1-D arrays, each through _repl_units) -> (its code units back to back, uint32
+        offsets[len + 1]).  ValueError: no entry, more than 256 entries, more than 4096 code units in all."""
+        repls = list(repls)
+        if not 1 <= len(repls) <= _lib.REPLACE_MAX_CHOICES:
+            raise ValueError("a replacement table holds 1 .. %d entries" % _lib.REPLACE_MAX_CHOICES)
+        parts = [Pattern._repl_units(r, char_width) for r in repls]
+        off = np.zeros(len(parts) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([u.size for u in parts])
+        if int(off[-1]) > _lib.REPLACE_MAX_UNITS:
+            raise ValueError("replacement table longer than %d code units" % _lib.REPLACE_MAX_UNITS)
+        return np.ascontiguousarray(np.concatenate(parts)), off
+
+    @staticmethod
+    def splice_each_packed(data, offsets, match_offsets, start, end, choice, repls, stream=None, out=None, out_start=0, lowest_bit=False):
+        """splice_packed with a replacement PER MATCH (needle_replace_each_lengths_packed_dev, torch cumsum,
+        needle_replace_each_fill_packed_dev on one stream): match m of the caller's CSR list is replaced by repls[c] when
+        0 <= c < len(repls) and KEPT as it is for every other c -> (out_data, out_offsets int64[n + 1]).  choice: int32, indexed like
+        start; c = choice[m], or with lowest_bit=True the index of the lowest set bit of the mask choice[m] (-1 for 0) -- what
+        PatternSet.matches_spans_packed returns goes in as it is.  repls: a list of str or 1-D arrays of code units (at most 256
+        entries, 4096 code units in all).  out / out_start, the one host read and numpy inputs: as splice_packed."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.uint16:
+                data = data.view(np.int16)
+            dev = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x).astype(dt)).to("cuda")
+            ch = np.ascontiguousarray(choice)
+            ch = ch.view(np.int32) if ch.dtype == np.uint32 else ch.astype(np.int32)
+            o, oo = Pattern.splice_each_packed(dev(np.concatenate([data, np.zeros((-data.nbytes) % 4 // data.itemsize, data.dtype)]), data.dtype),
+                                               dev(offsets, np.int64), dev(match_offsets, np.int64), dev(start, np.int32), dev(end, np.int32),
+                                               dev(ch, np.int32), repls, stream, lowest_bit=lowest_bit)
+            o = o.cpu().numpy()
+            return (o.view(np.uint16) if o.dtype == np.int16 else o), oo.cpu().numpy()
+        assert data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), "data: 1-D uint8 or (u)int16 code units"
+        for t, dt, what in ((offsets, torch.int64, "offsets"), (match_offsets, torch.int64, "match_offsets"), (start, torch.int32, "start"),
+                            (end, torch.int32, "end"), (choice, torch.int32, "choice")):
+            assert isinstance(t, torch.Tensor) and t.device == data.device and t.dtype == dt and t.dim() == 1 and t.is_contiguous(), what
+        n, dv, cw = offsets.numel() - 1, data.device, data.element_size()
+        assert n >= 0 and match_offsets.numel() == n + 1 and start.numel() == end.numel() == choice.numel()
+        r, roff = Pattern._repl_table(repls, cw)
+        form = _lib.CHOICE_LOWEST_BIT if lowest_bit else _lib.CHOICE_INDEX
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), cw, n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            s = one.cuda_stream
+            sp, ep, cp = (start.data_ptr(), end.data_ptr(), choice.data_ptr()) if start.numel() else (None, None, None)
+            lens = torch.empty(n, dtype=torch.int64, device=dv)
+            _check(L.needle_replace_each_lengths_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, cp, form, roff.ctypes.data, roff.size - 1,
+                                                            lens.data_ptr(), s))
+            out_off = torch.full((n + 1,), int(out_start), dtype=torch.int64, device=dv)
+            if n:
+                out_off[1:] += torch.cumsum(lens, 0)
+            total = int(out_off[-1].item())
+            if out is None:
+                room = torch.empty(total + 4, dtype=data.dtype, device=dv)  # (never an empty allocation: its pointer would be NULL)
+                out = room[:total]
+            else:
+                assert out.device == dv and out.dtype == data.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= total
+                room = out
+            _check(L.needle_replace_each_fill_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, cp, form, r.ctypes.data if r.size else None,
+                                                         roff.ctypes.data, roff.size - 1, out_off.data_ptr(), room.data_ptr(), s))
+        return out, out_off
+
     def replace_all_packed(self, data, offsets, repl, stream=None, out=None, out_start=0):
         """Every non-overlapping match of every packed row -- the matches find_all_packed files -- replaced by the literal `repl` (a str, or a
         1-D array of code units) -> (out_data, out_offsets[n + 1]): row r's result is out_data[out_offsets[r]:out_offsets[r + 1]].  What a
@@ -1443,6 +1510,68 @@ class PatternSet:
         off, st, en, masks = self.tag_matches_packed(pattern, data, offsets)
         return [list(zip(st[off[i]:off[i + 1]].tolist(), en[off[i]:off[i + 1]].tolist(), masks[off[i]:off[i + 1]].tolist()))
                 for i in range(len(strings))]
+
+    # ---- a rule list: rule i -> replacement i (needle_replace_each_*_packed_dev / needle_set_replace_each_packed_host)
+    def replace_each_packed(self, pattern, data, offsets, repls, stream=None, out=None, out_start=0):
+        """Every match of `pattern` in every packed row replaced by repls[i], i the LOWEST member of the set that matches the span whole
+        (first_member's convention: the first rule of an ordered rule list); a match no member matches is kept as it is ->
+        (out_data, out_offsets[n + 1]).  repls: one str or 1-D array of code units per member.  Device tensors: tag_matches_packed, then
+        Pattern.splice_each_packed(lowest_bit=True) on the same stream -- the masks go in as they are.  out / out_start: as
+        Pattern.splice_packed.  numpy data + offsets: needle_set_replace_each_packed_host."""
+        L = _lib.lib()
+        repls = list(repls)
+        if len(repls) != self.n_patterns:
+            raise ValueError("one replacement per member of the set: %d members, %d replacements" % (self.n_patterns, len(repls)))
+        if isinstance(data, np.ndarray) or not (type(data).__module__.startswith("torch") and data.is_cuda):
+            data = np.ascontiguousarray(data)
+            if data.dtype == np.int16:
+                data = data.view(np.uint16)
+            assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            r, roff = Pattern._repl_table(repls, data.dtype.itemsize)
+            v = _lib.PackedView()
+            v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+            out_off = np.zeros(n + 1, dtype=np.uint64)
+            capacity = max(1024, 2 * int(offsets[-1] - offsets[0]))
+            while True:  # (first with a guessed capacity, then with the exact total)
+                text = np.empty(capacity, dtype=data.dtype)
+                total = ctypes.c_uint64(0)
+                _check(L.needle_set_replace_each_packed_host(self._h, pattern._h, ctypes.byref(v), r.ctypes.data if r.size else None, roff.ctypes.data,
+                                                             roff.size - 1, out_off.ctypes.data, text.ctypes.data, capacity, ctypes.byref(total)))
+                if total.value <= capacity:
+                    return text[:total.value], out_off.astype(np.int64)
+                capacity = int(total.value)
+        off, st, en, masks = self.tag_matches_packed(pattern, data, offsets, stream)
+        return Pattern.splice_each_packed(data, offsets, off, st, en, masks, repls, stream=stream, out=out, out_start=out_start, lowest_bit=True)
+
+    def replace_each_strings(self, strings, repls, pattern=None):
+        """Every match of `pattern` (default: union_pattern()) in every str replaced by its rule's str of `repls` -> list[str] (UTF-16
+        code units, like java.lang.String): pack_strings + replace_each_packed's host entry."""
+        pattern = self.union_pattern() if pattern is None else pattern
+        data, offsets = pack_strings(strings)
+        text, off = self.replace_each_packed(pattern, data, offsets, repls)
+        return [text[off[i]:off[i + 1]].tobytes().decode("utf-16-le", "surrogatepass") for i in range(len(strings))]
+
+    def replace_each_bytes(self, rows, repls, pattern=None):
+        """Every match of `pattern` (default: union_pattern()) in every UTF-8 `bytes` row replaced by its rule's `bytes` of `repls` ->
+        list[bytes].  The composition of Pattern.replace_all_bytes: utf16_from_utf8_packed, find_all_packed and matches_spans_packed on the
+        UTF-16 view, utf8_positions_packed on start and end, then splice_each_packed at char width 1 on the ORIGINAL bytes -- no encoder
+        back to UTF-8, and ill-formed bytes outside replaced matches come back untouched."""
+        pattern = self.union_pattern() if pattern is None else pattern
+        repls = [np.frombuffer(bytes(r), dtype=np.uint8) for r in repls]
+        if len(repls) != self.n_patterns:
+            raise ValueError("one replacement per member of the set: %d members, %d replacements" % (self.n_patterns, len(repls)))
+        data, offsets = pack_bytes(rows)
+        d, o, _ = Pattern._utf8_dev(data, offsets)
+        units, uoff, _, _ = Pattern.utf16_from_utf8_packed(d, o)
+        moff, st, en = pattern.find_all_packed(units, uoff)
+        masks = self.matches_spans_packed(units, uoff, moff, st, en)
+        bs = Pattern.utf8_positions_packed(d, o, moff, st)
+        be = Pattern.utf8_positions_packed(d, o, moff, en)
+        text, off = Pattern.splice_each_packed(d, o, moff, bs, be, masks, repls, lowest_bit=True)
+        text, off = text.cpu().numpy(), off.cpu().numpy()
+        return [text[off[i]:off[i + 1]].tobytes() for i in range(len(rows))]
 
     def info(self, op="contained_in", char_width=1):
         """The groups of one op and char width (host-side: needs no GPU): {"n_patterns", "n_groups", "groups": [{"first_pattern",
