@@ -3,7 +3,7 @@ test_gpu_set_spans.py on the GPU).  A span list is (span_offsets int64[n_rows + 
 start / end[span_offsets[r] : span_offsets[r + 1]], relative to the row; span_offsets[0] may be > 0 (the entries below it are nobody's)."""
 import numpy as np
 
-from pattern_set_cases import SETS, gpu_batch
+from pattern_set_cases import GPU_RECIPE, SETS, gpu_batch, set_flags, split_case
 
 
 def clamp_span(s, e, n):
@@ -53,14 +53,16 @@ SHADOWED = {"logs8": {7}}
 _union = {}
 
 
-def union_spans(name):
-    """(rows, span list): the oracle's find_all of the set's union pattern over gpu_batch(name), computed once per set."""
-    if name not in _union:
+def union_spans(case):
+    """(rows, span list): the oracle's find_all of the set's union pattern (compiled with the set's flags) over the set's gpu_batch,
+    computed once per "name" or "name@8" / "name@16" (pattern_set_cases.split_case)."""
+    if case not in _union:
         from test_compile_matches_txt import oracle_for
-        o = oracle_for(union_regex(name), 0)[0]
-        rows = gpu_batch(name)
-        _union[name] = (rows, spans_from_lists([o.find_all(np.ascontiguousarray(r)) for r in rows]))
-    return _union[name]
+        name, dtype = split_case(case)
+        o = oracle_for(union_regex(name), set_flags(name))[0]
+        rows = gpu_batch(name, dtype=dtype, **GPU_RECIPE.get(name, {}))
+        _union[case] = (rows, spans_from_lists([o.find_all(np.ascontiguousarray(r)) for r in rows]))
+    return _union[case]
 
 
 SPAN_LENGTHS = [0, 1, 15, 16, 17, 31, 32, 33]

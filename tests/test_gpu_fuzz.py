@@ -2,7 +2,8 @@
 x random short haystacks over a small alphabet, all three ops through the packed entry points (ragged rows: the
 guarded kernels) and through a fixed-stride full-length batch (the unguarded kernels), against the oracle walking the
 same tables.  Whatever device mode the automaton lowers to (packed functions, pair table, uint8 / uint16 table) must
-give the reference's bits."""
+give the reference's bits.  And seeded random pattern sets (the generator of tests/test_pattern_set.py's fuzz) through the set
+kernels, against the members' oracles."""
 import random
 
 import numpy as np
@@ -123,3 +124,72 @@ def test_random_dictionaries(seed, lds):
     r = subprocess.run([sys.executable, "-c", mod.CODE, str(seed)], env=env, capture_output=True, text=True, cwd=root, timeout=900)
     assert "DICT-OK" in r.stdout, r.stdout[-1000:] + r.stderr[-3000:]
     assert ("mode 6, lengths form 1" if seed != 235 else "mode 6, lengths form 0") in r.stdout, r.stdout[-300:]  # (235: it does not fit 20 KB)
+
+
+# chosen on a CPU build: their first six sets hold 21 plans with 16-bit table elements; one set of seed 33 is cut into several groups
+SET_FUZZ_SEEDS = [3, 4, 12, 20, 33]
+SET_FUZZ_SETS_PER_SEED = 6
+_set_fuzz = {}
+
+
+def set_fuzz_seed(seed):
+    """Six random sets (pattern_set_cases.random_set, the generator of the CPU fuzz) per seed, per set and char width: 257 rows of
+    0 .. 70 chars and one of 9000; matches_packed and contained_in_packed into garbage-filled tensors against the members' oracles,
+    matches_spans_packed on random_spans of the same rows against the oracle per span -> (drawn, skipped, TABLE16 plans launched,
+    sets cut into groups), once per process."""
+    if seed in _set_fuzz:
+        return _set_fuzz[seed]
+    import torch
+    from pattern_set_cases import OPS_WIDTHS, fuzz_alphabet, fuzz_counters, oracle_masks, random_set
+    from set_spans_cases import random_spans, reference_span_masks
+    from test_gpu_packed_dev import device_packed
+    from test_gpu_pattern_set import device_masks
+    from test_gpu_set_spans import SENTINEL, device_span_masks
+    rng = random.Random(7000 + seed)  # (the CPU fuzz's stream: a seed's first sets are the same sets there)
+    nrng = np.random.default_rng(seed)
+    skipped = table16 = grouped = 0
+    for _ in range(SET_FUZZ_SETS_PER_SEED):
+        members, ps, oracles, infos = random_set(rng)
+        if ps is None:
+            skipped += 1
+            continue
+        t16, grp = fuzz_counters(infos)
+        table16, grouped = table16 + t16, grouped + grp
+        k = len(members)
+        for cw, dtype in ((1, np.uint8), (2, np.uint16)):
+            alpha = fuzz_alphabet(dtype)
+            rows = [nrng.choice(alpha, int(n)).astype(dtype) for n in nrng.integers(0, 71, 257)] + [nrng.choice(alpha, 9000).astype(dtype)]
+            what = ("seed", seed, "members", members, "char width", cw, [(op, [g["kernel_mode"] for g in infos[op, cw]["groups"]]) for op in ("matches", "contained_in")])
+            want_m, want_c = oracle_masks(oracles, rows, dtype)
+            data, offsets = device_packed(rows, dtype, lead=5, trail=7, junk=alpha[:9])
+            got_m, got_c = device_masks(ps, data, offsets, len(rows), garbage=True)
+            for op, got, want in (("matches", got_m, want_m), ("contained_in", got_c, want_c)):
+                bad = np.nonzero(got != want)[0]
+                assert bad.size == 0, (what, op, bad[:10], [len(rows[i]) for i in bad[:10]], got[bad[:5]], want[bad[:5]])
+                assert k == 32 or not (got >> np.uint32(k)).any(), (what, op, "bits at or above n_patterns")
+            spans = random_spans(rows, nrng, abs0=int(offsets[0]), cw=cw, lead=3)
+            got = device_span_masks(ps, data, offsets, spans, front=3, behind=5)
+            want = reference_span_masks(oracles, rows, spans)
+            lo, hi = int(spans[0][0]), int(spans[0][-1])
+            assert (got[:lo] == SENTINEL).all() and (got[hi:] == SENTINEL).all(), (what, "span entries that are nobody's were written")
+            bad = lo + np.nonzero(got[lo:hi] != want[lo:hi])[0]
+            assert bad.size == 0, (what, "spans", bad[:10], got[bad[:5]], want[bad[:5]], spans[1][bad[:5]], spans[2][bad[:5]])
+    _set_fuzz[seed] = (SET_FUZZ_SETS_PER_SEED, skipped, table16, grouped)
+    return _set_fuzz[seed]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SET_FUZZ_SEEDS)
+def test_random_pattern_sets(seed):
+    """Random sets through packed_set_kernel (both ops) and set_spans_kernel, 8-bit and UTF-16 rows, against the per-member oracle; a
+    failure names the seed and the members with their flags."""
+    print("seed %d: drawn %d, skipped %d, TABLE16 plans %d, grouped sets %d" % ((seed,) + set_fuzz_seed(seed)))
+
+
+@pytest.mark.gpu
+def test_random_pattern_sets_reach_16_bit_tables():
+    """Over all seeds (run here when their own tests were not): at least 4 launched plans have 16-bit table elements (info()), one
+    set at least runs as several groups, at most 5 % of the drawn sets are refused by PatternSet(...) or info()."""
+    drawn, skipped, table16, grouped = (sum(x) for x in zip(*[set_fuzz_seed(s) for s in SET_FUZZ_SEEDS]))
+    print("random sets: drawn %d, skipped %d, TABLE16 plans %d, grouped sets %d" % (drawn, skipped, table16, grouped))
+    assert table16 >= 4 and grouped >= 1 and skipped * 20 <= drawn, (drawn, skipped, table16, grouped)

@@ -239,7 +239,7 @@ def test_mask_form():
     assert flat.count(-1) > 10 and sum(1 for c in flat if c >= 5) > 10 and flat.count(1) > 10  # (n_repl 5: mask 0, bits at or above 5, entry 1)
 
 
-SET_NAMES = ["logs8", "nullable4", "u16b"]
+SET_NAMES = ["logs8", "nullable4", "u16b", "count260ci"]  # (count260ci: per-lane find-all, tags from a 16-bit table with flags, the splice)
 _sets = {}
 
 

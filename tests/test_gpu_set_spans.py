@@ -5,14 +5,15 @@ the 32-keyword set against a plain text comparison."""
 import numpy as np
 import pytest
 
-from pattern_set_cases import KW32, SETS, compile_set, oracle_masks, units
+from pattern_set_cases import KW32, SETS, assert_plan, compile_set, oracle_masks, split_case, units
 from set_spans_cases import random_spans, reference_span_masks, spans_from_lists, union_spans
 from test_gpu_pattern_set import JUNK, run_child
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0x5A5A5A5A
-NAMES = ["nullable4", "logs8", "u16b"]
+# (count260 / count260ci: the matches products have more than 255 states -- set_spans_kernel with 16-bit table elements, both widths)
+NAMES = ["nullable4", "logs8", "u16b", "count260", "count260@16", "count260ci@8", "count260ci"]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -31,9 +32,12 @@ def case(name):
     matches the members around the rows -- computed once per set."""
     if name not in _cache:
         from test_gpu_packed_dev import device_packed
-        ps, oracles, dtype = compile_set(name)
+        set_name, dtype = split_case(name)
+        ps, oracles, dtype = compile_set(set_name, dtype)
+        if set_name.startswith("count260"):  # the plan about to run: 16-bit table elements
+            assert assert_plan(set_name, ps, "matches", np.dtype(dtype).itemsize)["kernel_mode"] == 2
         rows = union_spans(name)[0]
-        data, offsets = device_packed(rows, dtype, lead=5, trail=7, junk=units(JUNK[name], dtype))
+        data, offsets = device_packed(rows, dtype, lead=5, trail=7, junk=units(JUNK[set_name], dtype))
         assert int(offsets[0]) > 0
         _cache[name] = (ps, oracles, dtype, rows, data, offsets)
     return _cache[name]

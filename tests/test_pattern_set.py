@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from pattern_set_cases import SETS, compile_set, oracle_masks, units, walk_tables
+from pattern_set_cases import (BIG, OLDER_GPU_SETS, OPS_WIDTHS, PLANS, SETS, TABLE8, alphabet_and_pieces, assert_plan, compile_set, fuzz_alphabet,
+                               fuzz_counters, ladder_shape, oracle_masks, random_set, split_case, units, walk_tables)
 
 NAMES = ["needle_pattern_set_create", "needle_pattern_set_destroy", "needle_pattern_set_info", "needle_pattern_set_get_tables",
          "needle_set_matches_packed_dev", "needle_set_contained_in_packed_dev", "needle_set_matches_packed_host",
@@ -91,8 +92,9 @@ def test_set_outlives_its_patterns(lib):
     assert [walk_tables(t, units(x, np.uint8), "matches") for x in ("xx7ab", "ab", "7", "x")] == [0, 2, 1, 0]
 
 
-def seeded_rows(name, n, seed):
-    _, dtype, alphabet, pieces = SETS[name]
+def seeded_rows(name, n, seed, dtype=None):
+    alphabet, pieces = alphabet_and_pieces(name, dtype)
+    dtype = SETS[name][1] if dtype is None else dtype
     rng = random.Random(seed)
     rows = []
     for i in range(n):
@@ -110,11 +112,15 @@ def seeded_rows(name, n, seed):
     return rows
 
 
-@pytest.mark.parametrize("name", ["nullable4", "logs8", "kw32", "mix16", "u16b"])
-def test_tables_walked_in_python_equal_the_oracle(lib, name):
-    ps, oracles, dtype = compile_set(name)
+NEW_SETS = ["edge255", "edge256", "count260", "count260ci", "tail5"]
+
+
+@pytest.mark.parametrize("case", ["nullable4", "logs8", "kw32", "mix16", "u16b"] + [s + w for s in NEW_SETS for w in ("@8", "@16")])
+def test_tables_walked_in_python_equal_the_oracle(lib, case):
+    name, dtype = split_case(case)
+    ps, oracles, dtype = compile_set(name, dtype)
     k = len(oracles)
-    rows = seeded_rows(name, 2000, 1234)
+    rows = seeded_rows(name, 2000, 1234, dtype)
     want_m, want_c = oracle_masks(oracles, rows, dtype)
     assert all(((want_c >> i) & 1).sum() >= 3 for i in range(k)), "every pattern is found in some rows"
     cw = np.dtype(dtype).itemsize
@@ -136,6 +142,78 @@ def test_tables_walked_in_python_equal_the_oracle(lib, name):
         bad = np.nonzero(got != want)[0]
         assert bad.size == 0, (name, op, bad[:5], [bytes(rows[i]) for i in bad[:3]], got[bad[:5]], want[bad[:5]])
         assert not (got >> np.uint32(k)).any() if k < 32 else True
+
+
+def test_kernel_modes_of_the_named_sets(lib):
+    """n_states, kernel_mode and lds_bytes of every (set, op, char width) a GPU test launches."""
+    # Why it matters: these numbers decide which instantiations of packed_set_kernel (op x width x element size x window bytes) and of
+    # set_spans_kernel (width x element size) each GPU test reaches.  The older sets are all 8-bit tables with 128-byte windows; the
+    # 16-bit tables, the 64-byte windows (lds_bytes > 65536) and the boundary between the element sizes are reached by PLANS' sets only.
+    for name in PLANS:
+        ps, _, _ = compile_set(name)
+        for op, cw in OPS_WIDTHS:
+            g = assert_plan(name, ps, op, cw)
+            waves, chb = ladder_shape(g["lds_bytes"])
+            assert (waves, chb) == ((16, 64) if g["lds_bytes"] > 65536 else (16, 128)), (name, op, cw, g)
+    big = [(n, op, cw) for n in PLANS for op, cw in OPS_WIDTHS if PLANS[n][2][OPS_WIDTHS.index((op, cw))] == BIG]
+    assert big == [("tail5", "matches", 1), ("tail5", "matches", 2), ("mix16", "contained_in", 1), ("mix16", "contained_in", 2)]
+    # edge255: the largest program with 8-bit elements (device states are the product's + 1: 0 is the sink, the highest is 255)
+    ps, _, _ = compile_set("edge255")
+    assert all(ps.tables(op, cw, 0)["n_states"] + 1 == 256 for op, cw in OPS_WIDTHS)
+    for name in OLDER_GPU_SETS:
+        ps, _, dtype = compile_set(name)
+        for op, cw in OPS_WIDTHS:
+            if cw == 1 and dtype == np.uint16:  # (the older UTF-16 set runs on UTF-16 rows only)
+                continue
+            for g in ps.info(op, cw)["groups"]:
+                assert g["kernel_mode"] == TABLE8 and g["lds_bytes"] <= 32768 and ladder_shape(g["lds_bytes"]) == (16, 128), (name, op, cw, g)
+
+
+FUZZ_SEEDS = range(6)   # chosen so that the conditions of test_random_sets_reach_both_table_widths_and_several_groups hold
+FUZZ_SETS_PER_SEED = 20
+_fuzz = {}
+
+
+def fuzz_seed(seed):
+    """The sets of one seed walked against the oracle, once per process -> (drawn, skipped, TABLE16 plans, sets cut into groups)."""
+    if seed in _fuzz:
+        return _fuzz[seed]
+    rng = random.Random(7000 + seed)
+    nrng = np.random.default_rng(seed)
+    rows = {cw: [nrng.choice(fuzz_alphabet(dt), int(n)).astype(dt) for n in nrng.integers(0, 24, 300)] for cw, dt in ((1, np.uint8), (2, np.uint16))}
+    skipped = table16 = grouped = 0
+    for _ in range(FUZZ_SETS_PER_SEED):
+        members, ps, oracles, infos = random_set(rng)
+        if ps is None:
+            skipped += 1
+            continue
+        t16, grp = fuzz_counters(infos)
+        table16, grouped = table16 + t16, grouped + grp
+        want = {cw: oracle_masks(oracles, rows[cw], rows[cw][0].dtype) for cw in (1, 2)}
+        for op, cw in OPS_WIDTHS:
+            got = np.zeros(len(rows[cw]), np.uint32)
+            for g in range(infos[op, cw]["n_groups"]):
+                t = ps.tables(op, cw, g)
+                got |= np.array([walk_tables(t, r, op) for r in rows[cw]], dtype=np.uint32)
+            bad = np.nonzero(got != want[cw][op == "contained_in"])[0]
+            assert bad.size == 0, (seed, members, op, cw, [rows[cw][i].tolist() for i in bad[:3]], got[bad[:3]], want[cw][op == "contained_in"][bad[:3]])
+    _fuzz[seed] = (FUZZ_SETS_PER_SEED, skipped, table16, grouped)
+    return _fuzz[seed]
+
+
+@pytest.mark.parametrize("seed", FUZZ_SEEDS)
+def test_random_sets_walked_in_python_equal_the_oracle(lib, seed):
+    """Sets of 1 .. 32 random regexes x random flag sets (pattern_set_cases.random_set): every group's product walked in Python, OR-ed,
+    against the members' own oracles -- both ops, both char widths, 300 rows of 0 .. 23 chars of the fuzz alphabet and the fold partners."""
+    print("seed %d: drawn %d, skipped %d, TABLE16 plans %d, grouped sets %d" % ((seed,) + fuzz_seed(seed)))
+
+
+def test_random_sets_reach_both_table_widths_and_several_groups(lib):
+    """Over all seeds (walked here when their own tests were not): at least 10 plans with 16-bit elements, at least one set cut into
+    several groups, at most 5 % of the drawn sets refused by PatternSet(...) or info()."""
+    drawn, skipped, table16, grouped = (sum(x) for x in zip(*[fuzz_seed(s) for s in FUZZ_SEEDS]))
+    print("random sets: drawn %d, skipped %d, TABLE16 plans %d, grouped sets %d" % (drawn, skipped, table16, grouped))
+    assert table16 >= 10 and grouped >= 1 and skipped * 20 <= drawn, (drawn, skipped, table16, grouped)
 
 
 def test_state_counts_are_of_the_accept_or_order(lib):
