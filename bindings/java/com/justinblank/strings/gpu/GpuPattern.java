@@ -370,6 +370,49 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         return result;
     }
 
+    /**
+     * The text of every non-overlapping match of every haystack -- the matches {@link #findAllStrings} reports: result[i] holds
+     * haystack i's matches in order ({@code grep -o}; an empty array where nothing matches).
+     */
+    public String[][] extractAllStrings(String[] haystacks) {
+        return gatherStrings(haystacks, 0);
+    }
+
+    /**
+     * Every haystack cut at its matches: the text in front of the first match, between the matches and behind the last; empty pieces
+     * are kept, a haystack without a match is one piece.  For patterns that do not match the empty string this is
+     * {@code haystack.split(regex, -1)}; for patterns that do it is not (find-all enumerates empty matches differently).
+     */
+    public String[][] splitStrings(String[] haystacks) {
+        return gatherStrings(haystacks, 1);
+    }
+
+    /** A sizing call, then the call that files the text (needle_gather_matches_packed_host). */
+    private String[][] gatherStrings(String[] haystacks, int mode) {
+        long[] offsets = new long[haystacks.length + 1];
+        char[] data = flatten(haystacks, offsets);
+        long[] spanOffsets = new long[haystacks.length + 1];
+        long[] totals = new long[2];
+        check(Native.gatherMatchesPackedHost(handle, data, offsets, mode, spanOffsets, null, null, totals), null);
+        if (totals[0] > Integer.MAX_VALUE - 8 || totals[1] > Integer.MAX_VALUE - 8) {
+            throw new IllegalArgumentException("the result does not fit an array: " + totals[0] + " strings, " + totals[1] + " chars");
+        }
+        long[] outOffsets = new long[(int) totals[0] + 1];
+        char[] out = new char[(int) totals[1]];
+        if (totals[0] > 0) {
+            check(Native.gatherMatchesPackedHost(handle, data, offsets, mode, spanOffsets, outOffsets, out, totals), null);
+        }
+        String[][] result = new String[haystacks.length][];
+        for (int i = 0; i < haystacks.length; i++) {
+            int a = (int) spanOffsets[i];
+            result[i] = new String[(int) spanOffsets[i + 1] - a];
+            for (int k = 0; k < result[i].length; k++) {
+                result[i][k] = new String(out, (int) outOffsets[a + k], (int) (outOffsets[a + k + 1] - outOffsets[a + k]));
+            }
+        }
+        return result;
+    }
+
     /** The haystacks' bytes back to back; offsets[i] is where haystack i begins. */
     private static byte[] flattenBytes(byte[][] haystacks, long[] offsets) {
         for (int i = 0; i < haystacks.length; i++) {

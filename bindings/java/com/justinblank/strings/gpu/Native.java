@@ -74,6 +74,14 @@ final class Native {
     static native int replaceAllPackedHost(long handle, char[] data, long[] offsets, char[] replacement, long[] outOffsets, char[] out, long[] total);
 
     /**
+     * needle_gather_matches_packed_host: every non-overlapping match of every packed haystack (mode 0) or every piece between the matches
+     * (mode 1) as a row of a new packed batch.  spanOffsets long[n + 1] (haystack i gave the output rows spanOffsets[i] ..
+     * spanOffsets[i + 1]) and totals long[2] (output rows, chars) are always filled; outOffsets long[rows + 1] and out char[chars]
+     * (null: size only) hold the result when both totals fit.
+     */
+    static native int gatherMatchesPackedHost(long handle, char[] data, long[] offsets, int mode, long[] spanOffsets, long[] outOffsets, char[] out, long[] totals);
+
+    /**
      * needle_find_packed16_packed_host / needle_find_packed8_packed_host: find() of every packed haystack with a row's result as
      * one int (start | end << 16; haystacks of at most 65 534 chars) or one short (start | (end - start) << 8, 0xFFFF no match,
      * 0xFFFE the match (0, 256); haystacks of at most 256 chars).  Longer haystacks: NEEDLE_ERR_UNSUPPORTED.

@@ -449,6 +449,39 @@ NATIVE(jint, replaceAllPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray da
     return rc;
 }
 
+/* needle_gather_matches_packed_host: data + offsets as packedHost; mode 0 (the matches) | 1 (the pieces between them); spanOffsets
+ * long[n + 1]; outOffsets long[spanCapacity + 1] and out char[unitCapacity] (each may be null: size only); totals long[2]: output rows,
+ * code units. */
+NATIVE(jint, gatherMatchesPackedHost)(JNIEnv *env, jclass c, jlong h, jcharArray data, jlongArray offsets, jint mode, jlongArray spanOffsets, jlongArray outOffsets, jcharArray out, jlongArray totals) {
+    if (!data || !offsets || !spanOffsets || !totals) return NEEDLE_ERR_INVALID;
+    const jsize n1 = (*env)->GetArrayLength(env, offsets);
+    if (n1 < 1 || (*env)->GetArrayLength(env, spanOffsets) < n1 || (*env)->GetArrayLength(env, totals) < 2) return NEEDLE_ERR_INVALID;
+    const jsize span_cap = outOffsets && (*env)->GetArrayLength(env, outOffsets) > 0 ? (*env)->GetArrayLength(env, outOffsets) - 1 : 0;
+    const jsize cap = out ? (*env)->GetArrayLength(env, out) : 0;
+    needle_packed_view v;
+    memset(&v, 0, sizeof(v));
+    jchar *d = (*env)->GetCharArrayElements(env, data, NULL);
+    jlong *o = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong *so = (*env)->GetLongArrayElements(env, spanOffsets, NULL);
+    jlong *oo = outOffsets ? (*env)->GetLongArrayElements(env, outOffsets, NULL) : NULL;
+    jchar *text = cap ? (*env)->GetCharArrayElements(env, out, NULL) : NULL;
+    v.data = d;
+    v.char_width = 2;
+    v.n_rows = (uint64_t)(n1 - 1);
+    v.offsets = (const uint64_t *)o;
+    uint64_t ts = 0, tu = 0;
+    int rc = needle_gather_matches_packed_host((const needle_pattern *)(intptr_t)h, &v, (int)mode, (uint64_t *)so, span_cap ? (uint64_t *)oo : NULL,
+                                               (uint64_t)span_cap, text, (uint64_t)cap, &ts, &tu);
+    jlong jt[2] = {(jlong)ts, (jlong)tu};
+    (*env)->SetLongArrayRegion(env, totals, 0, 2, jt);
+    (*env)->ReleaseCharArrayElements(env, data, d, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, offsets, o, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, spanOffsets, so, 0);
+    if (oo) (*env)->ReleaseLongArrayElements(env, outOffsets, oo, 0);
+    if (text) (*env)->ReleaseCharArrayElements(env, out, text, 0);
+    return rc;
+}
+
 /* needle_find_packed16_packed_host / needle_find_packed8_packed_host: data + offsets as packedHost; bitmap long[(n + 63) / 64];
  * the results int[n] (16) or short[n] (8). */
 static jint find_packed_compact_host(JNIEnv *env, jlong h, jcharArray data, jlongArray offsets, jlongArray bitmap, jarray out, int bits) {

@@ -10,6 +10,7 @@ NEEDLE_OK, ERR_INVALID, ERR_SYNTAX, ERR_COMPILE, ERR_UNSUPPORTED, ERR_DEVICE = 0
 REPLACE_MAX_UNITS = 4096  # NEEDLE_REPLACE_MAX_UNITS
 REPLACE_MAX_CHOICES = 256  # NEEDLE_REPLACE_MAX_CHOICES
 CHOICE_INDEX, CHOICE_LOWEST_BIT = 0, 1  # NEEDLE_CHOICE_INDEX, NEEDLE_CHOICE_LOWEST_BIT
+GATHER_MATCHES, GATHER_PIECES = 0, 1  # NEEDLE_GATHER_MATCHES, NEEDLE_GATHER_PIECES
 UTF8_MAX_EXPANSION = 1  # NEEDLE_UTF8_MAX_EXPANSION: units(row) <= bytes(row)
 
 EXPORTS = [
@@ -25,6 +26,8 @@ EXPORTS = [
     "needle_find_packed8_packed_dev", "needle_find_packed16_packed_host", "needle_find_packed8_packed_host",
     "needle_replace_all_lengths_packed_dev", "needle_replace_all_fill_packed_dev", "needle_replace_all_packed_host",
     "needle_replace_each_lengths_packed_dev", "needle_replace_each_fill_packed_dev", "needle_set_replace_each_packed_host",
+    "needle_gather_spans_lengths_packed_dev", "needle_gather_spans_fill_packed_dev", "needle_split_spans_packed_dev", "needle_gather_chunk_spans",
+    "needle_gather_matches_packed_host",
     "needle_utf16_lengths_from_utf8_packed_dev", "needle_utf16_from_utf8_packed_dev", "needle_utf8_positions_packed_dev", "needle_utf8_window_bytes",
     "needle_contained_in_utf8_packed_host", "needle_find_all_csr_utf8_packed_host",
     "needle_pattern_set_create", "needle_pattern_set_destroy", "needle_pattern_set_info", "needle_pattern_set_get_tables",
@@ -175,6 +178,12 @@ def lib():
     L.needle_replace_each_lengths_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, I, VP, ctypes.c_uint32, VP, VP]
     L.needle_replace_each_fill_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, I, VP, VP, ctypes.c_uint32, VP, VP, VP]
     L.needle_set_replace_each_packed_host.argtypes = [VP, VP, P(PackedView), VP, VP, ctypes.c_uint32, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]
+    L.needle_gather_spans_lengths_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, VP]
+    L.needle_gather_spans_fill_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, VP, VP]
+    L.needle_split_spans_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, VP, VP, VP]
+    L.needle_gather_chunk_spans.argtypes = []
+    L.needle_gather_chunk_spans.restype = ctypes.c_uint32
+    L.needle_gather_matches_packed_host.argtypes = [VP, P(PackedView), I, VP, VP, ctypes.c_uint64, VP, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64)]
     L.needle_utf16_lengths_from_utf8_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP]
     L.needle_utf16_from_utf8_packed_dev.argtypes = [P(PackedView), VP, VP, VP]
     L.needle_utf8_positions_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP]

@@ -1641,6 +1641,77 @@ int needle_replace_each_fill_packed_dev(const needle_packed_view *v, const uint6
     return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_each_fill_packed_dev");
 }
 
+// Spans of packed rows as a new packed batch (needle_gather.hip): pure functions of (text, span list) -- no pattern, no route.  The checks
+// the three entries share, then the kernels' arguments; n_rows == 0 has returned before the CU count is asked for.
+static int gather_args(const needle_packed_view *v, const uint64_t *d_span_offsets, const int32_t *d_start, const int32_t *d_end, GatherArgs *a) {
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    if (!d_span_offsets) return fail(NEEDLE_ERR_INVALID, "span offsets is NULL");
+    if ((d_start == nullptr) != (d_end == nullptr)) return fail(NEEDLE_ERR_INVALID, "start / end: one of them is NULL");
+    memset(a, 0, sizeof(*a));
+    a->data = (const uint8_t *)v->data;
+    a->in_off = v->offsets;
+    a->n_rows = v->n_rows;
+    a->cw = v->char_width;
+    a->span_off = d_span_offsets;
+    a->start = d_start;
+    a->end = d_end;
+    return NEEDLE_OK;
+}
+static int gather_cus(int *cus) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return NEEDLE_OK;
+}
+
+// (d_start / d_end may be NULL when the list is empty, which only the device knows: the kernels then dereference neither)
+int needle_gather_spans_lengths_packed_dev(const needle_packed_view *v, const uint64_t *d_span_offsets, const int32_t *d_start,
+                                           const int32_t *d_end, uint64_t *d_out_lengths, void *stream_) {
+    GatherArgs a;
+    int rc = gather_args(v, d_span_offsets, d_start, d_end, &a), cus = 0;
+    if (rc) return rc;
+    if (d_start && !d_out_lengths) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (v->n_rows == 0 || !d_start) return NEEDLE_OK;
+    if ((rc = gather_cus(&cus))) return rc;
+    a.out_len = d_out_lengths;
+    HIP_TRY(launch_gather_lengths(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+int needle_gather_spans_fill_packed_dev(const needle_packed_view *v, const uint64_t *d_span_offsets, const int32_t *d_start,
+                                        const int32_t *d_end, const uint64_t *d_out_offsets, void *d_out_data, void *stream_) {
+    GatherArgs a;
+    int rc = gather_args(v, d_span_offsets, d_start, d_end, &a), cus = 0;
+    if (rc) return rc;
+    if (!d_out_offsets || !d_out_data) return fail(NEEDLE_ERR_INVALID, "output offsets / buffer is NULL");
+    if (((uintptr_t)d_out_data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "output data must be 4-byte aligned");
+    if (v->n_rows == 0 || !d_start) return NEEDLE_OK;
+    if ((rc = gather_cus(&cus))) return rc;
+    a.out_off = d_out_offsets;
+    a.out = (uint8_t *)d_out_data;
+    HIP_TRY(launch_gather_fill(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+int needle_split_spans_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_start, const int32_t *d_end,
+                                  uint64_t *d_piece_offsets, int32_t *d_piece_start, int32_t *d_piece_end, void *stream_) {
+    GatherArgs a;
+    int rc = gather_args(v, d_match_offsets, d_start, d_end, &a), cus = 0;
+    if (rc) return rc;
+    if (!d_piece_offsets || !d_piece_start || !d_piece_end) return fail(NEEDLE_ERR_INVALID, "piece offsets / output buffer is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if ((rc = gather_cus(&cus))) return rc;
+    a.piece_off = d_piece_offsets;
+    a.piece_start = d_piece_start;
+    a.piece_end = d_piece_end;
+    HIP_TRY(launch_split_spans(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+uint32_t needle_gather_chunk_spans(void) { return gather_chunk_spans(); }
+
 // The UTF-8 front door (needle_utf8.hip): pure functions of the text (and a position list) -- no pattern, no route.  The checks all
 // three entries share, then the kernels' arguments and the device's CU count (n_rows == 0: not reached).
 static int utf8_view_check(const needle_packed_view *v) {

@@ -836,6 +836,111 @@ int needle_set_replace_each_packed_host(const needle_pattern_set *s, const needl
     return replace_packed_host("set_replace_each_packed_host", p, v, repl, 0, s, repl_offsets, n_repl, out_offsets, out_data, capacity, total);
 }
 
+// Every match (NEEDLE_GATHER_MATCHES) or every piece between the matches (NEEDLE_GATHER_PIECES) of a packed HOST batch as the rows of a
+// new packed batch.  Per chunk of rows (20 bytes per row: offset, count, match offset): upload, count pass, prefix sum here; then in
+// sub-ranges of at most NEEDLE_HOST_RESULT_BYTES of matches: CSR fill, the split list (pieces), lengths, prefix sum here into the caller's
+// out_offsets, and -- while both of the caller's buffers have room -- gather and download.  A sub-range's output is at most its rows' text
+// (the matches are disjoint, the pieces their complement): the chunk budget bounds it.
+int needle_gather_matches_packed_host(const needle_pattern *p, const needle_packed_view *v, int mode, uint64_t *span_offsets, uint64_t *out_offsets,
+                                      uint64_t span_capacity, void *out_data, uint64_t unit_capacity, uint64_t *total_spans, uint64_t *total_units) {
+    const char *who = "gather_matches_packed_host";
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (mode != NEEDLE_GATHER_MATCHES && mode != NEEDLE_GATHER_PIECES)
+        return fail(NEEDLE_ERR_INVALID, "mode is neither NEEDLE_GATHER_MATCHES nor NEEDLE_GATHER_PIECES");
+    if (!span_offsets || !total_spans || !total_units || (span_capacity && !out_offsets) || (unit_capacity && !out_data))
+        return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    span_offsets[0] = 0;
+    if (out_offsets) out_offsets[0] = 0;
+    *total_spans = *total_units = 0;
+    if (v->n_rows == 0) return NEEDLE_OK;
+    if ((rc = check_packed_rows(v, ~0ull, ""))) return rc;
+    const uint64_t cw = v->char_width;
+    const bool pieces = mode == NEEDLE_GATHER_PIECES;
+    struct At {
+        uint64_t cnt, moff;
+    };
+    std::vector<uint32_t> counts;
+    std::vector<uint64_t> moff, lens, local;
+    uint64_t spans = 0, units = 0; // the output rows and code units so far
+    rc = for_packed_chunks(
+        v, 8 + 4 + 8, 1, who,
+        [&](Slab &lay, uint64_t nr) {
+            const uint64_t cnt = lay.add(nr * 4);
+            return At{cnt, lay.add((nr + 1) * 8)};
+        },
+        [&](const needle_packed_view &dv, const ChunkOut &out, uint64_t r0, const At &o) {
+            const uint64_t nr = dv.n_rows;
+            int rc = needle_count_matches_packed_dev(p, &dv, (uint32_t *)(out.d + o.cnt), nullptr);
+            moff.assign(nr + 1, 0);
+            if (rc || (rc = csr_offsets(out, o.cnt, 0, nr, counts, moff.data()))) return rc;
+            for (uint64_t r = 0; r < nr; ++r) span_offsets[r0 + r + 1] = span_offsets[r0 + r] + (moff[r + 1] - moff[r]) + (pieces ? 1 : 0);
+            uint64_t *d_moff = (uint64_t *)(out.d + o.moff);
+            const std::vector<RowRange> ranges = csr_ranges(moff.data(), 0, nr, std::max<uint64_t>(host_result_bytes() / 8, 1));
+            uint64_t big_m = 0, big_l = 0, big_r = 0; // the most matches, list entries and rows of a sub-range
+            for (const RowRange &rg : ranges) {
+                const uint64_t nm = moff[rg.second] - moff[rg.first], sn = rg.second - rg.first;
+                big_m = std::max(big_m, nm), big_l = std::max(big_l, pieces ? nm + sn : nm), big_r = std::max(big_r, sn);
+            }
+            Slab lay;
+            const uint64_t o_s = lay.add(big_m * 4), o_e = lay.add(big_m * 4), o_po = lay.add(pieces ? (big_r + 1) * 8 : 0);
+            const uint64_t o_ps = lay.add(pieces ? big_l * 4 : 0), o_pe = lay.add(pieces ? big_l * 4 : 0), o_len = lay.add((big_l + 1) * 8);
+            DevSlab list;
+            hipError_t e = list.alloc(lay.total());
+            if (e != hipSuccess) return hip_fail(e, "gather_matches_packed_host lists");
+            int32_t *d_s = (int32_t *)(list.d + o_s), *d_e = (int32_t *)(list.d + o_e);
+            for (const RowRange &rg : ranges) {
+                const uint64_t a = rg.first, sn = rg.second - rg.first, nm = moff[rg.second] - moff[a], nl = pieces ? nm + sn : nm;
+                spans += nl;
+                if (!nl) continue;
+                local.resize(sn + 1);
+                for (uint64_t r = 0; r <= sn; ++r) local[r] = moff[a + r] - moff[a];
+                HIP_TRY(hipMemcpy(d_moff, local.data(), (sn + 1) * 8, hipMemcpyHostToDevice));
+                needle_packed_view sv = dv;
+                sv.offsets = dv.offsets + a;
+                sv.n_rows = sn;
+                int more = 0;
+                if (nm && (rc = needle_find_all_csr_packed_dev(p, &sv, d_moff, d_s, d_e, &more, nullptr))) return rc;
+                if (more) return fail(NEEDLE_ERR_DEVICE, "gather_matches_packed_host: count pass and fill pass disagree");
+                const uint64_t *d_lo = d_moff; // the list that is gathered
+                const int32_t *d_ls = d_s, *d_le = d_e;
+                if (pieces) {
+                    uint64_t *d_po = (uint64_t *)(list.d + o_po);
+                    int32_t *d_ps = (int32_t *)(list.d + o_ps), *d_pe = (int32_t *)(list.d + o_pe);
+                    if ((rc = needle_split_spans_packed_dev(&sv, d_moff, nm ? d_s : nullptr, nm ? d_e : nullptr, d_po, d_ps, d_pe, nullptr))) return rc;
+                    d_lo = d_po, d_ls = d_ps, d_le = d_pe;
+                }
+                uint64_t *d_len = (uint64_t *)(list.d + o_len);
+                if ((rc = needle_gather_spans_lengths_packed_dev(&sv, d_lo, d_ls, d_le, d_len, nullptr))) return rc;
+                lens.resize(nl + 1);
+                e = hipMemcpy(lens.data(), d_len, nl * 8, hipMemcpyDeviceToHost);
+                if (e != hipSuccess) return hip_fail(e, "gather_matches_packed_host lengths");
+                uint64_t sum = 0; // lens becomes the sub-range's own exclusive prefix sum
+                for (uint64_t m = 0; m < nl; ++m) {
+                    const uint64_t l = lens[m];
+                    lens[m] = sum;
+                    sum += l;
+                }
+                lens[nl] = sum;
+                const uint64_t span0 = spans - nl, unit0 = units;
+                units += sum;
+                if (spans > span_capacity) continue;
+                for (uint64_t m = 1; m <= nl; ++m) out_offsets[span0 + m] = unit0 + lens[m];
+                if (units > unit_capacity || !sum) continue;
+                DevSlab text;
+                if ((e = text.alloc(sum * cw)) != hipSuccess) return hip_fail(e, "gather_matches_packed_host text");
+                HIP_TRY(hipMemcpy(d_len, lens.data(), (nl + 1) * 8, hipMemcpyHostToDevice));
+                if ((rc = needle_gather_spans_fill_packed_dev(&sv, d_lo, d_ls, d_le, d_len, text.d, nullptr))) return rc;
+                e = hipMemcpy((uint8_t *)out_data + unit0 * cw, text.d, sum * cw, hipMemcpyDeviceToHost);
+                if (e != hipSuccess) return hip_fail(e, "gather_matches_packed_host download");
+            }
+            return (int)NEEDLE_OK;
+        });
+    if (rc == NEEDLE_OK) *total_spans = spans, *total_units = units;
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------------
 // UTF-8 packed host rows: transcoded on the device, byte positions back
 // ------------------------------------------------------------------------------------------------

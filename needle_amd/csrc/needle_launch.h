@@ -7,6 +7,7 @@
 #include <functional>
 #include "needle_device.h"
 #include "needle_find_all.h"
+#include "needle_gather.h"
 #include "needle_ngram.h"
 #include "needle_replace.h"
 #include "needle_replace_each.h"
@@ -79,6 +80,12 @@ hipError_t launch_replace_fill(const ReplaceArgs &a, int n_cus, hipStream_t stre
 // needle_replace_each.hip: the splice with a replacement per match out of a table (needle_replace_each_*_packed_dev)
 hipError_t launch_replace_each_lengths(const ReplaceEachArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_replace_each_fill(const ReplaceEachArgs &a, int n_cus, hipStream_t stream);
+// needle_gather.hip: spans of packed rows as a new packed batch (needle_gather_spans_*_packed_dev), a match list's complement
+// (needle_split_spans_packed_dev); the spans the fill kernel tables at once
+hipError_t launch_gather_lengths(const GatherArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_gather_fill(const GatherArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_split_spans(const GatherArgs &a, int n_cus, hipStream_t stream);
+uint32_t gather_chunk_spans();
 // needle_utf8.hip: UTF-8 packed rows -> UTF-16 packed rows (lengths, fill), unit positions -> byte offsets; the text a wave takes per step
 hipError_t launch_utf8_lengths(const Utf8Args &a, int n_cus, hipStream_t stream);
 hipError_t launch_utf8_fill(const Utf8Args &a, int n_cus, hipStream_t stream);

@@ -1204,6 +1204,230 @@ class Pattern:
         text, off = self.replace_all_packed(data, offsets, repl)
         return [text[off[i]:off[i + 1]].tobytes().decode("utf-16-le", "surrogatepass") for i in range(len(strings))]
 
+    # ---- spans of packed rows as a new packed batch: extract, split, select (needle_gather_spans_*_packed_dev,
+    # needle_split_spans_packed_dev, needle_gather_matches_packed_host)
+    @staticmethod
+    def _gather_host_args(data, arrays):
+        """numpy packed data (padded to whole 4 bytes) and int arrays on the device, for the static methods' numpy form."""
+        import torch
+        data = np.ascontiguousarray(data)
+        if data.dtype == np.uint16:
+            data = data.view(np.int16)
+        pad = np.zeros(4 // data.itemsize + (-data.nbytes) % 4 // data.itemsize, data.dtype)
+        up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x).astype(dt)).to("cuda")
+        return up(np.concatenate([data, pad]), data.dtype), [up(x, dt) for x, dt in arrays]
+
+    @staticmethod
+    def _gather_host_text(text):
+        text = text.cpu().numpy()
+        return text.view(np.uint16) if text.dtype == np.int16 else text
+
+    @staticmethod
+    def _gather_check(data, tensors):
+        import torch
+        assert data.dim() == 1 and data.is_contiguous() and data.dtype in (torch.uint8, torch.int16, torch.uint16), "data: 1-D uint8 or (u)int16 code units"
+        for t, dt, what in tensors:
+            assert isinstance(t, torch.Tensor) and t.device == data.device and t.dtype == dt and t.dim() == 1 and t.is_contiguous(), what
+
+    @staticmethod
+    def gather_spans_packed(data, offsets, span_offsets, start, end, stream=None, out=None, out_start=0):
+        """The spans of a CSR list over packed rows as a NEW packed batch (needle_gather_spans_lengths_packed_dev, torch cumsum,
+        needle_gather_spans_fill_packed_dev on one stream): span m of row r -- span_offsets int64[n + 1], start / end int32, positions
+        relative to the row, find_all_packed's result or any list: repeated, overlapping, reversed and out-of-row spans are clamped into
+        their row -- gives the output row row_r[s':e'] -> (out_data, out_offsets).  out_offsets is indexed like start, one entry more:
+        for a list that fills start / end (span_offsets[0] == 0, span_offsets[n] == len(start)) it is the new batch's offsets as they
+        are; entries outside the list repeat their neighbour.  out: optional caller-owned tensor of the rows' dtype; the result then
+        starts at its code unit out_start (appending) and out_offsets are positions in `out`; units outside the result are left as they
+        are.  The one host read is the total.  numpy inputs are uploaded, gathered on the device and brought back."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            d, (o, so, st, en) = Pattern._gather_host_args(data, ((offsets, np.int64), (span_offsets, np.int64), (start, np.int32), (end, np.int32)))
+            text, oo = Pattern.gather_spans_packed(d, o, so, st, en, stream)
+            return Pattern._gather_host_text(text), oo.cpu().numpy()
+        Pattern._gather_check(data, ((offsets, torch.int64, "offsets"), (span_offsets, torch.int64, "span_offsets"), (start, torch.int32, "start"),
+                                     (end, torch.int32, "end")))
+        n, dv, m = offsets.numel() - 1, data.device, start.numel()
+        assert n >= 0 and span_offsets.numel() == n + 1 and end.numel() == m
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            s = one.cuda_stream
+            sp, ep = (start.data_ptr(), end.data_ptr()) if m else (None, None)
+            lens = torch.zeros(m + 1, dtype=torch.int64, device=dv)  # (entries outside the list stay 0; never an empty allocation)
+            _check(L.needle_gather_spans_lengths_packed_dev(ctypes.byref(v), span_offsets.data_ptr(), sp, ep, lens.data_ptr(), s))
+            out_off = torch.full((m + 1,), int(out_start), dtype=torch.int64, device=dv)
+            if m:
+                out_off[1:] += torch.cumsum(lens[:m], 0)
+            total = int(out_off[-1].item())
+            if out is None:
+                room = torch.empty(total + 4, dtype=data.dtype, device=dv)  # (never an empty allocation: its pointer would be NULL)
+                out = room[:total]
+            else:
+                assert out.device == dv and out.dtype == data.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= total
+                room = out
+            if room.numel():  # (an `out` of no units has no address to hand over, and nothing is to be written)
+                _check(L.needle_gather_spans_fill_packed_dev(ctypes.byref(v), span_offsets.data_ptr(), sp, ep, out_off.data_ptr(), room.data_ptr(), s))
+        return out, out_off
+
+    @staticmethod
+    def split_spans_packed(data, offsets, match_offsets, start, end, stream=None):
+        """A match list's complement (needle_split_spans_packed_dev): the c matches of a row give c + 1 pieces -- the text in front of the
+        first match, between the matches, behind the last; empty pieces are kept -> (piece_offsets int64[n + 1], piece_start int32,
+        piece_end int32), a span list for gather_spans_packed.  The one host read is the number of matches.  numpy inputs are uploaded."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            d, (o, mo, st, en) = Pattern._gather_host_args(data, ((offsets, np.int64), (match_offsets, np.int64), (start, np.int32), (end, np.int32)))
+            return tuple(x.cpu().numpy() for x in Pattern.split_spans_packed(d, o, mo, st, en, stream))
+        Pattern._gather_check(data, ((offsets, torch.int64, "offsets"), (match_offsets, torch.int64, "match_offsets"), (start, torch.int32, "start"),
+                                     (end, torch.int32, "end")))
+        n, dv = offsets.numel() - 1, data.device
+        assert n >= 0 and match_offsets.numel() == n + 1 and start.numel() == end.numel()
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            pieces = int((match_offsets[-1] - match_offsets[0]).item()) + n
+            po = torch.zeros(n + 1, dtype=torch.int64, device=dv)
+            room = torch.empty(2 * pieces + 1, dtype=torch.int32, device=dv)  # (never an empty allocation: its pointer would be NULL)
+            sp, ep = (start.data_ptr(), end.data_ptr()) if start.numel() else (None, None)
+            _check(L.needle_split_spans_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, po.data_ptr(), room.data_ptr(),
+                                                   room.data_ptr() + 4 * pieces, one.cuda_stream))
+        return po, room[:pieces], room[pieces:2 * pieces]
+
+    def _gather_matches_host(self, mode, data, offsets):
+        """needle_gather_matches_packed_host on numpy data + offsets: first with guessed capacities, then with the exact totals."""
+        L = _lib.lib()
+        data = np.ascontiguousarray(data)
+        if data.dtype == np.int16:
+            data = data.view(np.uint16)
+        assert data.ndim == 1 and data.dtype in (np.uint8, np.uint16), "data: 1-D uint8/uint16 code units"
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.ctypes.data, data.dtype.itemsize, n, offsets.ctypes.data
+        span_off = np.zeros(n + 1, dtype=np.uint64)
+        span_cap, unit_cap = max(1024, 2 * n), max(1024, int(offsets[-1] - offsets[0]))
+        while True:
+            out_off = np.zeros(span_cap + 1, dtype=np.uint64)
+            text = np.empty(unit_cap, dtype=data.dtype)
+            spans, units = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            _check(L.needle_gather_matches_packed_host(self._h, ctypes.byref(v), mode, span_off.ctypes.data, out_off.ctypes.data, span_cap,
+                                                       text.ctypes.data, unit_cap, ctypes.byref(spans), ctypes.byref(units)))
+            if spans.value <= span_cap and units.value <= unit_cap:
+                return text[:units.value], out_off[:spans.value + 1].astype(np.int64), span_off.astype(np.int64)
+            span_cap, unit_cap = max(span_cap, int(spans.value)), max(unit_cap, int(units.value))
+
+    def extract_all_packed(self, data, offsets, stream=None, out=None, out_start=0):
+        """Every non-overlapping match of every packed row -- the matches find_all_packed files -- as the rows of a NEW packed batch (grep
+        -o, regexp_extract_all) -> (out_data, out_offsets, span_offsets int64[n + 1]): input row r gave the output rows span_offsets[r] ..
+        span_offsets[r + 1], output row m is out_data[out_offsets[m]:out_offsets[m + 1]].  (out_data, out_offsets) goes into every
+        *_packed method as it is.  Device tensors: find_all_packed through the pattern's own route, then gather_spans_packed, on one
+        stream; out / out_start as gather_spans_packed.  numpy data + offsets: needle_gather_matches_packed_host."""
+        if isinstance(data, np.ndarray) or not (type(data).__module__.startswith("torch") and data.is_cuda):
+            return self._gather_matches_host(_lib.GATHER_MATCHES, data, offsets)
+        off, st, en = self.find_all_packed(data, offsets, stream=stream)
+        text, oo = Pattern.gather_spans_packed(data, offsets, off, st, en, stream=stream, out=out, out_start=out_start)
+        return text, oo, off
+
+    def split_packed(self, data, offsets, stream=None, out=None, out_start=0):
+        """Every packed row cut at its matches -- the text in front of, between and behind them, empty pieces kept -- as the rows of a NEW
+        packed batch -> (out_data, out_offsets, span_offsets) as extract_all_packed.  For patterns that do not match the empty string it
+        is re.split / String.split(regex, -1); for nullable patterns it is neither (find-all's enumeration of empty matches differs).
+        Device tensors: find_all_packed, split_spans_packed, gather_spans_packed on one stream.  numpy data + offsets:
+        needle_gather_matches_packed_host."""
+        if isinstance(data, np.ndarray) or not (type(data).__module__.startswith("torch") and data.is_cuda):
+            return self._gather_matches_host(_lib.GATHER_PIECES, data, offsets)
+        off, st, en = self.find_all_packed(data, offsets, stream=stream)
+        po, ps, pe = Pattern.split_spans_packed(data, offsets, off, st, en, stream=stream)
+        text, oo = Pattern.gather_spans_packed(data, offsets, po, ps, pe, stream=stream, out=out, out_start=out_start)
+        return text, oo, po
+
+    @staticmethod
+    def select_rows_packed(data, offsets, bits, stream=None, out=None, out_start=0):
+        """The rows a bitmap selects as a NEW packed batch -> (out_data, out_offsets int64[selected + 1]).  bits: the bitmap words of
+        contained_in_packed / matches_packed (int64 / uint64, bit r of word r // 64), or a bool tensor of n entries.  The list is built
+        with torch -- span_offsets = the prefix sum of the bits, every span (0, 2^31 - 1): the clamp makes it the whole row -- and goes
+        through gather_spans_packed.  numpy inputs are uploaded and the result brought back."""
+        import torch
+        if isinstance(data, np.ndarray):
+            b = np.ascontiguousarray(bits)
+            b = (b.astype(bool), np.bool_) if b.dtype == np.bool_ else (b.view(np.int64) if b.dtype == np.uint64 else b.astype(np.int64), np.int64)
+            d, (o, bt) = Pattern._gather_host_args(data, ((offsets, np.int64), b))
+            text, oo = Pattern.select_rows_packed(d, o, bt, stream)
+            return Pattern._gather_host_text(text), oo.cpu().numpy()
+        n, dv = offsets.numel() - 1, data.device
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            if bits.dtype == torch.bool:
+                assert bits.numel() == n, "bits: one bool per row"
+                hit = bits
+            else:
+                assert bits.numel() >= (n + 63) // 64, "bits: ceil(n / 64) bitmap words"
+                hit = ((bits.view(torch.int64).unsqueeze(1) >> torch.arange(64, device=dv)) & 1).reshape(-1)[:n].bool()
+            so = torch.zeros(n + 1, dtype=torch.int64, device=dv)
+            if n:
+                torch.cumsum(hit, 0, out=so[1:])
+            chosen = int(so[-1].item())
+            st = torch.zeros(chosen, dtype=torch.int32, device=dv)
+            en = torch.full((chosen,), 0x7FFFFFFF, dtype=torch.int32, device=dv)
+        return Pattern.gather_spans_packed(data, offsets, so, st, en, stream=stream, out=out, out_start=out_start)
+
+    def grep_packed(self, data, offsets, stream=None, out=None, out_start=0):
+        """The packed rows that contain a match, as a NEW packed batch -> (out_data, out_offsets): contained_in_packed, then
+        select_rows_packed -- what grep prints."""
+        if isinstance(data, np.ndarray):
+            return Pattern.select_rows_packed(data, offsets, self.contained_in_packed(data, offsets), stream)
+        return Pattern.select_rows_packed(data, offsets, self.contained_in_packed(data, offsets, stream=stream), stream=stream, out=out, out_start=out_start)
+
+    @staticmethod
+    def _rows_of(text, off, span_off, decode):
+        text, off, span_off = np.asarray(text), np.asarray(off), np.asarray(span_off)
+        rows = [decode(text[off[m]:off[m + 1]]) for m in range(off.size - 1)]
+        return [rows[int(span_off[r]):int(span_off[r + 1])] for r in range(span_off.size - 1)]
+
+    def extract_all_strings(self, strings):
+        """Every match of every str, as text -> list of list[str] (re.findall for patterns without groups): pack_strings +
+        extract_all_packed."""
+        data, offsets = pack_strings(strings)
+        text, off, so = self.extract_all_packed(data, offsets)
+        return Pattern._rows_of(text, off, so, lambda u: u.tobytes().decode("utf-16-le", "surrogatepass"))
+
+    def split_strings(self, strings):
+        """Every str cut at its matches -> list of list[str] (re.split for patterns that do not match the empty string): pack_strings +
+        split_packed."""
+        data, offsets = pack_strings(strings)
+        text, off, so = self.split_packed(data, offsets)
+        return Pattern._rows_of(text, off, so, lambda u: u.tobytes().decode("utf-16-le", "surrogatepass"))
+
+    def grep_strings(self, strings):
+        """The strs that contain a match -> list[str]: pack_strings + grep_packed."""
+        data, offsets = pack_strings(strings)
+        text, off = self.grep_packed(data, offsets)
+        return [text[off[m]:off[m + 1]].tobytes().decode("utf-16-le", "surrogatepass") for m in range(off.size - 1)]
+
+    def _gather_bytes(self, rows, split):
+        data, offsets = pack_bytes(rows)
+        d, o, _ = Pattern._utf8_dev(data, offsets)
+        moff, bs, be = self.find_all_utf8_packed(d, o)
+        if split:
+            moff, bs, be = Pattern.split_spans_packed(d, o, moff, bs, be)
+        text, off = Pattern.gather_spans_packed(d, o, moff, bs, be)
+        return Pattern._rows_of(text.cpu().numpy(), off.cpu().numpy(), moff.cpu().numpy(), lambda u: u.tobytes())
+
+    def extract_all_bytes(self, rows):
+        """Every match of every UTF-8 `bytes` row, as bytes -> list of list[bytes]: find_all_utf8_packed's byte positions, then
+        gather_spans_packed at char width 1 on the ORIGINAL bytes -- the gather never sees a pattern, and no encoder back to UTF-8 is
+        involved."""
+        return self._gather_bytes(rows, False)
+
+    def split_bytes(self, rows):
+        """Every UTF-8 `bytes` row cut at its matches -> list of list[bytes]; the bytes of ill-formed input outside the matches come back
+        untouched (find_all_utf8_packed, split_spans_packed, gather_spans_packed at char width 1)."""
+        return self._gather_bytes(rows, True)
+
     # ---- UTF-8 packed rows: transcoded on the device, byte positions back (needle_utf16_*_from_utf8_packed_dev,
     # needle_utf8_positions_packed_dev, needle_*_utf8_packed_host)
     @staticmethod
