@@ -12,6 +12,7 @@ REPLACE_MAX_CHOICES = 256  # NEEDLE_REPLACE_MAX_CHOICES
 CHOICE_INDEX, CHOICE_LOWEST_BIT = 0, 1  # NEEDLE_CHOICE_INDEX, NEEDLE_CHOICE_LOWEST_BIT
 GATHER_MATCHES, GATHER_PIECES = 0, 1  # NEEDLE_GATHER_MATCHES, NEEDLE_GATHER_PIECES
 UTF8_MAX_EXPANSION = 1  # NEEDLE_UTF8_MAX_EXPANSION: units(row) <= bytes(row)
+LINES_KEEP_ENDS = 1  # NEEDLE_LINES_KEEP_ENDS
 
 EXPORTS = [
     "needle_version", "needle_last_error", "needle_device_count", "needle_trim_scratch", "needle_tuning_info", "needle_compile", "needle_pattern_from_tables",
@@ -30,6 +31,7 @@ EXPORTS = [
     "needle_gather_matches_packed_host",
     "needle_utf16_lengths_from_utf8_packed_dev", "needle_utf16_from_utf8_packed_dev", "needle_utf8_positions_packed_dev", "needle_utf8_window_bytes",
     "needle_contained_in_utf8_packed_host", "needle_find_all_csr_utf8_packed_host",
+    "needle_lines_tile_units", "needle_lines_tiles", "needle_lines_count_packed_dev", "needle_lines_fill_packed_dev",
     "needle_pattern_set_create", "needle_pattern_set_destroy", "needle_pattern_set_info", "needle_pattern_set_get_tables",
     "needle_set_matches_packed_dev", "needle_set_contained_in_packed_dev", "needle_set_matches_packed_host", "needle_set_contained_in_packed_host",
     "needle_set_matches_spans_packed_dev", "needle_set_tag_matches_packed_host",
@@ -191,6 +193,12 @@ def lib():
     L.needle_utf8_window_bytes.restype = ctypes.c_uint32
     L.needle_contained_in_utf8_packed_host.argtypes = [VP, P(PackedView), VP, VP]
     L.needle_find_all_csr_utf8_packed_host.argtypes = [VP, P(PackedView), VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64), VP]
+    L.needle_lines_tile_units.argtypes = [ctypes.c_uint32]
+    L.needle_lines_tile_units.restype = ctypes.c_uint32
+    L.needle_lines_tiles.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+    L.needle_lines_tiles.restype = ctypes.c_uint64
+    L.needle_lines_count_packed_dev.argtypes = [P(PackedView), ctypes.c_uint64, ctypes.c_uint32, VP, VP, VP]
+    L.needle_lines_fill_packed_dev.argtypes = [P(PackedView), ctypes.c_uint64, ctypes.c_uint32, VP, VP, VP, VP, VP, VP]
     L.needle_pattern_set_create.argtypes = [P(VP), I, P(VP)]
     L.needle_pattern_set_destroy.argtypes = [VP]
     L.needle_pattern_set_destroy.restype = None

@@ -1783,6 +1783,66 @@ int needle_utf8_positions_packed_dev(const needle_packed_view *v, const uint64_t
 
 uint32_t needle_utf8_window_bytes(void) { return utf8_window_bytes(); }
 
+// Documents cut at their line terminators (needle_lines.hip): pure functions of the text -- no pattern, no route.  The checks both entries
+// share, then the kernels' arguments; an empty batch has returned before the CU count is asked for.
+static int lines_args(const needle_packed_view *v, uint64_t data_units, uint32_t flags, LinesArgs *a) {
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    if (flags & ~NEEDLE_LINES_KEEP_ENDS) return fail(NEEDLE_ERR_INVALID, "unknown flag bits");
+    memset(a, 0, sizeof(*a));
+    a->data = (const uint8_t *)v->data;
+    a->in_off = v->offsets;
+    a->n_rows = v->n_rows;
+    a->cw = v->char_width;
+    a->data_units = data_units;
+    a->tiles = needle_lines_tiles(data_units, v->char_width);
+    return NEEDLE_OK;
+}
+
+uint32_t needle_lines_tile_units(uint32_t char_width) { return lines_tile_units(char_width); }
+
+uint64_t needle_lines_tiles(uint64_t data_units, uint32_t char_width) {
+    const uint64_t t = lines_tile_units(char_width);
+    return t ? data_units / t + (data_units % t != 0) : 0;
+}
+
+int needle_lines_count_packed_dev(const needle_packed_view *v, uint64_t data_units, uint32_t flags, uint64_t *d_tile_lines, uint64_t *d_tile_units,
+                                  void *stream_) {
+    LinesArgs a;
+    int rc = lines_args(v, data_units, flags, &a), cus = 0;
+    if (rc) return rc;
+    if (!d_tile_lines) return fail(NEEDLE_ERR_INVALID, "tile lines is NULL");
+    if (!(flags & NEEDLE_LINES_KEEP_ENDS) && !d_tile_units) return fail(NEEDLE_ERR_INVALID, "tile units is NULL without NEEDLE_LINES_KEEP_ENDS");
+    if (v->n_rows == 0 || data_units == 0) return NEEDLE_OK;
+    if ((rc = gather_cus(&cus))) return rc;
+    a.tile_lines = d_tile_lines;
+    a.tile_units = (flags & NEEDLE_LINES_KEEP_ENDS) ? nullptr : d_tile_units;
+    HIP_TRY(launch_lines_count(a, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
+int needle_lines_fill_packed_dev(const needle_packed_view *v, uint64_t data_units, uint32_t flags, const uint64_t *d_tile_line_base,
+                                 const uint64_t *d_tile_unit_base, uint64_t *d_out_offsets, void *d_out_data, uint64_t *d_doc_line_offsets,
+                                 void *stream_) {
+    LinesArgs a;
+    int rc = lines_args(v, data_units, flags, &a), cus = 0;
+    if (rc) return rc;
+    const bool keep = (flags & NEEDLE_LINES_KEEP_ENDS) != 0;
+    if (!d_tile_line_base || !d_out_offsets) return fail(NEEDLE_ERR_INVALID, "tile line base / output offsets is NULL");
+    if (!keep && (!d_tile_unit_base || !d_out_data)) return fail(NEEDLE_ERR_INVALID, "tile unit base / output buffer is NULL without NEEDLE_LINES_KEEP_ENDS");
+    if (!keep && ((uintptr_t)d_out_data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "output data must be 4-byte aligned");
+    if (v->n_rows == 0 || data_units == 0) return NEEDLE_OK;
+    if ((rc = gather_cus(&cus))) return rc;
+    a.line_base = d_tile_line_base;
+    a.unit_base = keep ? nullptr : d_tile_unit_base;
+    a.out_off = d_out_offsets;
+    a.out = keep ? nullptr : (uint8_t *)d_out_data;
+    a.doc_lines = d_doc_line_offsets;
+    HIP_TRY(launch_lines_fill(a, keep, cus, (hipStream_t)stream_));
+    return NEEDLE_OK;
+}
+
 int needle_find_all_compact16_packed_dev(const needle_pattern *cp, const needle_packed_view *v, uint32_t max_per_row, uint64_t *d_offsets,
                                          uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, int *more, void *stream_) {
     needle_pattern *p = const_cast<needle_pattern *>(cp);

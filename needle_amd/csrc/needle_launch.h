@@ -8,6 +8,7 @@
 #include "needle_device.h"
 #include "needle_find_all.h"
 #include "needle_gather.h"
+#include "needle_lines.h"
 #include "needle_ngram.h"
 #include "needle_replace.h"
 #include "needle_replace_each.h"
@@ -91,6 +92,10 @@ hipError_t launch_utf8_lengths(const Utf8Args &a, int n_cus, hipStream_t stream)
 hipError_t launch_utf8_fill(const Utf8Args &a, int n_cus, hipStream_t stream);
 hipError_t launch_utf8_positions(const Utf8Args &a, int n_cus, hipStream_t stream);
 uint32_t utf8_window_bytes();
+// needle_lines.hip: packed documents cut at their line terminators (needle_lines_*_packed_dev); the units of a tile per char width
+hipError_t launch_lines_count(const LinesArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_lines_fill(const LinesArgs &a, bool keep_ends, int n_cus, hipStream_t stream);
+uint32_t lines_tile_units(uint32_t char_width);
 // needle_lower.cpp (NEEDLE_PREFILTER)
 int ngram_level();
 

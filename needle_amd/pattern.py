@@ -1513,8 +1513,9 @@ class Pattern:
         data, offsets, host = Pattern._utf8_dev(data, offsets)
         one = torch.cuda.current_stream(data.device) if stream is None else torch.cuda.ExternalStream(stream, device=data.device)
         with torch.cuda.device(data.device), torch.cuda.stream(one):
-            units, uoff, _, _ = Pattern.utf16_from_utf8_packed(data, offsets, stream=one.cuda_stream)
-            words = self._run_packed_dev(op, units, uoff, one.cuda_stream, None)
+            # (the caller's `stream` as it came: None stays None, and both steps then take torch's current stream)
+            units, uoff, _, _ = Pattern.utf16_from_utf8_packed(data, offsets, stream=stream)
+            words = self._run_packed_dev(op, units, uoff, stream, None)
         return words.cpu().numpy().view(np.uint64) if host else words
 
     def _utf8_host_view(self, data, offsets):
@@ -1589,6 +1590,35 @@ class Pattern:
         text, off = Pattern.splice_packed(d, o, moff, bs, be, np.frombuffer(bytes(repl), dtype=np.uint8))
         text, off = text.cpu().numpy(), off.cpu().numpy()
         return [text[off[i]:off[i + 1]].tobytes() for i in range(len(rows))]
+
+    # ---- a file as a packed batch: lines_packed in front of the UTF-8 chain (needle_lines_*_packed_dev)
+    def _grep_lines(self, buf):
+        """A UTF-8 file -> (its lines without terminators as a packed device batch, the bitmap words of the lines that contain a match):
+        upload, lines_packed, contained_in_utf8_packed on the current stream; None for a file without lines."""
+        import torch
+        a = np.frombuffer(bytes(buf), dtype=np.uint8)
+        if a.size == 0:
+            return None
+        d = torch.from_numpy(np.concatenate([a, np.zeros(4 + (-a.size) % 4, np.uint8)])).to("cuda")
+        text, lo, _ = lines_packed(d[:a.size])
+        return (text, lo, self.contained_in_utf8_packed(text, lo)) if lo.numel() > 1 else None
+
+    def grep_lines_bytes(self, buf):
+        """The lines of the UTF-8 file `buf` (bytes) that contain a match, without their terminators -> list[bytes]: what
+        [l for l in buf.splitlines() if re.search(regex, l.decode("utf-8", "replace"))] gives.  The file is uploaded whole and cut into
+        lines on the device (lines_packed); the lines go through contained_in_utf8_packed and select_rows_packed as the byte rows they
+        are; one download of the chosen lines.  The host never sees a row before that."""
+        r = self._grep_lines(buf)
+        if r is None:
+            return []
+        text, off = Pattern.select_rows_packed(r[0], r[1], r[2])
+        text, off = text.cpu().numpy(), off.cpu().numpy()
+        return [text[off[i]:off[i + 1]].tobytes() for i in range(off.size - 1)]
+
+    def count_lines_bytes(self, buf):
+        """The number of lines of the UTF-8 file `buf` that contain a match (grep -c): grep_lines_bytes without the gather."""
+        r = self._grep_lines(buf)
+        return 0 if r is None else int(unpack_bitmap(r[2], r[1].numel() - 1).sum())
 
     @staticmethod
     def rows_from_packed(data, offsets, row_stride=None, stream=None):
@@ -1890,6 +1920,85 @@ def pack_bytes(rows):
     if rows:
         offsets[1:] = np.cumsum([len(x) for x in rows])
     return np.frombuffer(b"".join(bytes(x) for x in rows), dtype=np.uint8).copy(), offsets
+
+
+def lines_packed(data, offsets=None, keep_ends=False, stream=None, out=None, out_start=0, line_start=0):
+    """A packed batch of DOCUMENTS (text buffers: files, multi-line cells) cut at its line terminators into a packed batch of LINES, on the
+    device -> (text, line_offsets, doc_line_offsets): bytes.splitlines() / String.lines() of every document, one after the other.
+    data: 1-D uint8 or int16 / uint16 code units; offsets: int64[n + 1], None = one document, the whole tensor.  '\\n', '\\r' and '\\r\\n' end a
+    line (whole code units: U+2028, U+0085 and 0x0A0A are ordinary characters), an unterminated tail is a line, the empty document has
+    none.  keep_ends=False: text is a NEW compacted buffer without any terminator unit and line_offsets index it; out / out_start: a
+    caller-owned tensor of data's dtype, the result starting at its unit out_start (appending), units outside the result left as they are;
+    text is then `out` itself, whole, as the gather entries return it (the result ends at line_offsets[-1]).
+    keep_ends=True: a line includes its terminator, text is `data` itself and line_offsets are positions in it (out / out_start are not
+    used).  line_offsets: int64[line_start + lines + 1], line j of the result at entries line_start + j and + 1, the entries in front equal
+    to entry line_start; (text, line_offsets[line_start:]) goes into every *_packed method.  doc_line_offsets: int64[n + 1], document d
+    gave the lines doc_line_offsets[d] .. doc_line_offsets[d + 1] (counted from line_start).
+    needle_lines_count_packed_dev, torch cumsum, needle_lines_fill_packed_dev on one stream; the one host read is the two totals.  numpy
+    inputs are uploaded and the results brought back (with out_start > 0 the out_start units in front of the result are not initialised, as
+    in the gather entries' numpy form).  An empty input gives the empty batch without a call of the library."""
+    import torch
+    L = _lib.lib()
+    if isinstance(data, np.ndarray):
+        off = np.array([0, data.size], np.int64) if offsets is None else offsets
+        d, (o,) = Pattern._gather_host_args(data, ((off, np.int64),))
+        text, lo, dlo = lines_packed(d[:data.size], o, keep_ends, stream, None, out_start, line_start)
+        host = np.ascontiguousarray(data)
+        return host if keep_ends else Pattern._gather_host_text(text).view(host.dtype), lo.cpu().numpy(), dlo.cpu().numpy()
+    Pattern._gather_check(data, ())
+    dv, units = data.device, data.numel()
+    if offsets is None:
+        offsets = torch.tensor([0, units], dtype=torch.int64, device=dv)
+    Pattern._gather_check(data, ((offsets, torch.int64, "offsets"),))
+    n = offsets.numel() - 1
+    assert n >= 0 and out_start >= 0 and line_start >= 0
+    if out is not None:
+        assert not keep_ends, "keep_ends: the text is data itself"
+        assert out.device == dv and out.dtype == data.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= out_start
+    one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+    with torch.cuda.device(dv), torch.cuda.stream(one):
+        s = one.cuda_stream
+        if n == 0 or units == 0:  # no line anywhere
+            first = offsets[:1] if keep_ends else torch.full((1,), int(out_start), dtype=torch.int64, device=dv)
+            text = data if keep_ends else (out if out is not None else torch.empty(out_start + 4, dtype=data.dtype, device=dv))[:out_start]
+            return text, first.repeat(line_start + 1), torch.full((n + 1,), int(line_start), dtype=torch.int64, device=dv)
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        flags = _lib.LINES_KEEP_ENDS if keep_ends else 0
+        tiles = L.needle_lines_tiles(units, data.element_size())
+        counts = torch.empty(2 * tiles, dtype=torch.int64, device=dv)
+        bases = torch.empty(2 * (tiles + 1), dtype=torch.int64, device=dv)
+        _check(L.needle_lines_count_packed_dev(ctypes.byref(v), units, flags, counts.data_ptr(), None if keep_ends else counts.data_ptr() + 8 * tiles, s))
+        lb, ub = bases[:tiles + 1], bases[tiles + 1:]
+        lb[0], ub[0] = int(line_start), int(out_start)
+        torch.cumsum(counts[:tiles], 0, out=lb[1:])
+        lb[1:] += int(line_start)
+        if not keep_ends:
+            torch.cumsum(counts[tiles:], 0, out=ub[1:])
+            ub[1:] += int(out_start)
+        line_end, unit_end = (int(x) for x in torch.stack([lb[-1], ub[-1]]).cpu())
+        line_off = torch.empty(line_end + 1, dtype=torch.int64, device=dv)
+        doc_off = torch.empty(n + 1, dtype=torch.int64, device=dv)
+        if keep_ends:
+            text, room = data, None
+        elif out is None:
+            room = torch.empty(unit_end + 4, dtype=data.dtype, device=dv)  # (never an empty allocation: its pointer would be NULL)
+            text = room[:unit_end]
+        else:
+            assert out.numel() >= unit_end
+            text = room = out
+        _check(L.needle_lines_fill_packed_dev(ctypes.byref(v), units, flags, lb.data_ptr(), None if keep_ends else ub.data_ptr(), line_off.data_ptr(),
+                                              None if keep_ends else room.data_ptr(), doc_off.data_ptr(), s))
+        if line_start:
+            line_off[:line_start] = line_off[line_start]
+    return text, line_off, doc_off
+
+
+def lines_of_bytes(buf, keep_ends=False):
+    """bytes.splitlines(keep_ends) of `buf` on the device -> list[bytes]: upload, lines_packed, one download."""
+    a = np.frombuffer(bytes(buf), dtype=np.uint8)
+    text, off, _ = lines_packed(a, keep_ends=keep_ends)
+    return [text[off[i]:off[i + 1]].tobytes() for i in range(off.size - 1)]
 
 
 def unpack_bitmap(words, n_rows):

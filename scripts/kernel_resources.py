@@ -3,6 +3,7 @@
 rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel,
 of the pattern-set kernel of span lists (needle_set_spans.h) and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
 (needle_replace.hip, needle_replace_each.hip: 4 waves per workgroup, static LDS) and of the gather kernels (needle_gather.hip: the same) and of the UTF-8 kernels (needle_utf8.hip: the same)
+and of the line-splitting kernels (needle_lines.hip: one workgroup of 256 lanes per tile, static LDS)
 (cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
 LDS is the program plus one window (the tile) per wave, sized at launch: listed as the window per wave.
@@ -21,7 +22,7 @@ for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", 
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
            "needle_packed_set1", "needle_packed_set2", "needle_set_spans1", "needle_set_spans2",
            "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2",
-           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace", "needle_replace_each", "needle_gather", "needle_utf8"):
+           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace", "needle_replace_each", "needle_gather", "needle_utf8", "needle_lines"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
                                          "-S", "-o", out, os.path.join(CSRC, tu + ".hip")], stderr=subprocess.DEVNULL)))
@@ -123,3 +124,9 @@ for k, sc, v in sorted(rows):
     m = re.search(r"utf8_(lengths|fill|positions)_kernel", k)
     if m:
         print("%4d %4d %6d  utf8 %s" % (sc, v, lds.get(k, 0), m.group(1)))
+# the line-splitting kernels (needle_lines.hip): count per char width, fill per char width and mode
+print("line-splitting kernels (needle_lines.hip): scratch bytes / VGPRs / LDS bytes per workgroup / kernel")
+for k, sc, v in sorted(rows):
+    m = re.search(r"lines_(count|fill)_kernelILi(\d)E(?:Lb(\d)E)?", k)
+    if m:
+        print("%4d %4d %6d  lines %-5s cw%s %s" % (sc, v, lds.get(k, 0), m.group(1), m.group(2), {None: "", "0": "strip", "1": "keep ends"}[m.group(3)]))
