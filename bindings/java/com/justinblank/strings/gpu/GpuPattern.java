@@ -287,7 +287,7 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         long[] offsets = new long[haystacks.length + 1];
         char[] data = flatten(haystacks, offsets);
         long[] bitmap = new long[(haystacks.length + 63) / 64];
-        check(Native.findPacked16Host(handle, data, offsets, bitmap, startEnd), null);
+        check(Native.findPacked16PackedHost(handle, data, offsets, bitmap, startEnd), null);
         return bitmap;
     }
 
@@ -299,7 +299,7 @@ public final class GpuPattern implements Pattern, AutoCloseable {
         long[] offsets = new long[haystacks.length + 1];
         char[] data = flatten(haystacks, offsets);
         long[] bitmap = new long[(haystacks.length + 63) / 64];
-        check(Native.findPacked8Host(handle, data, offsets, bitmap, startLen), null);
+        check(Native.findPacked8PackedHost(handle, data, offsets, bitmap, startLen), null);
         return bitmap;
     }
 

@@ -5,7 +5,12 @@ package com.justinblank.strings.gpu;
  * library's status code except where noted, and the shim (bindings/jni/needle_jni.c) never throws -- exceptions
  * are raised on the Java side from the status (see GpuPattern.check).
  *
- * NOT COMPILED IN THE BUILD CONTAINER (no JDK, no jni.h); shipped as source for a maintainer with a JDK.
+ * The shim is compiled and exercised against a stand-in jni.h and a fake JNIEnv (tests/jni/, tests/test_jni_shim.py,
+ * tests/test_gpu_jni_shim.py), and every declaration below is checked against its C definition there (name, return
+ * type, parameter list) -- a signature check: this file itself has never been compiled (no JDK in the build image) and
+ * the shim has never been loaded by a JVM.  No native is overloaded, so each has the short JNI symbol name.
+ * An array argument is required unless its description says it may be null; a required array that is null or shorter
+ * than described gives NEEDLE_ERR_INVALID.
  */
 final class Native {
     static {
@@ -86,9 +91,9 @@ final class Native {
      * one int (start | end << 16; haystacks of at most 65 534 chars) or one short (start | (end - start) << 8, 0xFFFF no match,
      * 0xFFFE the match (0, 256); haystacks of at most 256 chars).  Longer haystacks: NEEDLE_ERR_UNSUPPORTED.
      */
-    static native int findPacked16Host(long handle, char[] data, long[] offsets, long[] bitmap, int[] startEnd);
+    static native int findPacked16PackedHost(long handle, char[] data, long[] offsets, long[] bitmap, int[] startEnd);
 
-    static native int findPacked8Host(long handle, char[] data, long[] offsets, long[] bitmap, short[] startLen);
+    static native int findPacked8PackedHost(long handle, char[] data, long[] offsets, long[] bitmap, short[] startLen);
 
     /**
      * Pattern sets (needle_pattern_set_*): 1 .. 32 patterns answered in one pass over a packed batch.  setCreate copies the patterns'
