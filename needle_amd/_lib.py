@@ -13,6 +13,8 @@ CHOICE_INDEX, CHOICE_LOWEST_BIT = 0, 1  # NEEDLE_CHOICE_INDEX, NEEDLE_CHOICE_LOW
 GATHER_MATCHES, GATHER_PIECES = 0, 1  # NEEDLE_GATHER_MATCHES, NEEDLE_GATHER_PIECES
 UTF8_MAX_EXPANSION = 1  # NEEDLE_UTF8_MAX_EXPANSION: units(row) <= bytes(row)
 LINES_KEEP_ENDS = 1  # NEEDLE_LINES_KEEP_ENDS
+CAPTURES_MAX_GROUPS = 16  # NEEDLE_CAPTURES_MAX_GROUPS
+CAPTURES_REASONS = {0: None, 1: "NULLABLE_LOOP", 2: "NO_REGEX", 3: "TOO_MANY_GROUPS", 4: "TOO_BIG"}  # NEEDLE_CAPTURES_*
 
 EXPORTS = [
     "needle_version", "needle_last_error", "needle_device_count", "needle_trim_scratch", "needle_tuning_info", "needle_compile", "needle_pattern_from_tables",
@@ -35,6 +37,7 @@ EXPORTS = [
     "needle_pattern_set_create", "needle_pattern_set_destroy", "needle_pattern_set_info", "needle_pattern_set_get_tables",
     "needle_set_matches_packed_dev", "needle_set_contained_in_packed_dev", "needle_set_matches_packed_host", "needle_set_contained_in_packed_host",
     "needle_set_matches_spans_packed_dev", "needle_set_tag_matches_packed_host",
+    "needle_pattern_captures_info", "needle_pattern_captures_tables", "needle_captures_spans_packed_dev",
     "needle_multi_create", "needle_multi_destroy", "needle_multi_device_count", "needle_multi_stream", "needle_multi_transport", "needle_multi_scan",
     "needle_multi_sync", "needle_scan_host_multi", "needle_multi_unique_id", "needle_multi_create_rank",
     "needle_multi_all_gather_u64", "needle_multi_gather_i32",
@@ -90,6 +93,11 @@ class PrefilterInfo2(ctypes.Structure):
 class SetInfo(ctypes.Structure):
     _fields_ = ([("n_patterns", ctypes.c_int32), ("n_groups", ctypes.c_int32)] +
                 [(k, ctypes.c_int32 * 32) for k in ("first_pattern", "pattern_count", "n_states", "n_columns", "kernel_mode", "lds_bytes")])
+
+
+class CapturesInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("available", "reason", "n_groups", "n_states", "n_cols", "max_threads", "n_slots", "n_op_lists",
+                                              "n_ops", "start", "init_op", "lds_bytes")]
 
 
 _lib = None
@@ -210,6 +218,9 @@ def lib():
         getattr(L, n).argtypes = [VP, P(PackedView), VP]
     L.needle_set_matches_spans_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP, VP]
     L.needle_set_tag_matches_packed_host.argtypes = [VP, VP, P(PackedView), VP, VP, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]
+    L.needle_pattern_captures_info.argtypes = [VP, I, P(CapturesInfo)]
+    L.needle_pattern_captures_tables.argtypes = [VP, I, VP, VP, VP, ctypes.c_size_t, VP, ctypes.c_size_t, VP, ctypes.c_size_t, VP, ctypes.c_size_t]
+    L.needle_captures_spans_packed_dev.argtypes = [VP, P(PackedView), VP, VP, VP, VP, VP, ctypes.c_uint64, VP]
     L.needle_matcher_create.argtypes = [VP, VP, ctypes.c_size_t, P(VP)]
     L.needle_matcher_destroy.argtypes = [VP]
     L.needle_matcher_destroy.restype = None

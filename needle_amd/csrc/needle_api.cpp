@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/needle_hip.h"
+#include "needle_captures.h"
 #include "needle_device.h"
 #include "needle_find_all.h"
 #include "needle_internal.h"
@@ -176,7 +177,22 @@ struct needle_pattern {
     std::mutex ml_mu;       // guards the one-time match-length analysis only: scans of programs that exist already do not wait for it
     int ml_state = 0;       // 0: not analysed yet, 1: find-all can report starts as end - length (ml), -1: it cannot
     MatchLengths ml;
+    // The capture program (needle_captures.h) is built from the regex TEXT, which only needle_compile has: kept here, not in the blob.
+    bool has_regex = false;
+    std::u16string regex;
+    int regex_flags = 0;
+    std::mutex cap_mu;      // guards everything below
+    bool cap_built = false;
+    int cap_rc = NEEDLE_OK; // (the second parse's own status: NEEDLE_OK wherever compile_regex accepted the regex)
+    std::string cap_err;
+    CapTables cap;
+    bool cap_lowered[2] = {false, false};
+    CapProgram cap_prog[2];                             // [char_width - 1]
+    std::map<std::pair<int, int>, uint8_t *> cap_resident; // (device, char_width) -> the program in that device's HBM
+    std::map<int, int> cap_cus;                         // device -> CU count
     ~needle_pattern() {
+        for (auto &kv : cap_resident)
+            if (kv.second) (void)hipFree(kv.second);
         for (auto &kv : cache) {
             if (kv.second.ng_stream) (void)hipStreamSynchronize(kv.second.ng_stream); // (a stats copy may still be on its way into h_ng_stats)
             if (kv.second.d_blob) (void)hipFree(kv.second.d_blob);
@@ -1947,6 +1963,9 @@ int needle_compile(const uint16_t *regex, size_t n, int flags, needle_pattern **
         delete p;
         return fail(NEEDLE_ERR_COMPILE, err);
     }
+    p->has_regex = true;
+    p->regex.assign((const char16_t *)regex, n);
+    p->regex_flags = flags;
     *out = p;
     return NEEDLE_OK;
 }
@@ -2784,6 +2803,153 @@ int needle_set_matches_spans_packed_dev(const needle_pattern_set *cs, const need
         a.store = g == 0 ? 1u : 0u;
         HIP_TRY(launch_set_spans(cw, a, n_cus, (hipStream_t)stream_));
     }
+    return NEEDLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Capturing groups (needle_captures.h: the tagged DFA and its LDS program; needle_captures_spans.h: the kernel)
+// ------------------------------------------------------------------------------------------------
+static const char *const kCapReasonNames[] = {"available", "NEEDLE_CAPTURES_NULLABLE_LOOP", "NEEDLE_CAPTURES_NO_REGEX", "NEEDLE_CAPTURES_TOO_MANY_GROUPS",
+                                              "NEEDLE_CAPTURES_TOO_BIG"};
+
+// The pattern's capture tables and the program of `cw`, built on first use (under cap_mu).  *reason: CAP_OK or why there is none.
+static int captures_program(needle_pattern *p, int cw, const CapProgram **prog, int *reason, std::string *why) {
+    std::lock_guard<std::mutex> lk(p->cap_mu);
+    if (!p->cap_built) {
+        if (!p->has_regex) {
+            p->cap.reason = CAP_NO_REGEX;
+            p->cap.n_groups = -1;
+            p->cap.why = "the pattern was not made by needle_compile: it has no regex text";
+        } else {
+            p->cap_rc = build_captures(p->regex, p->regex_flags, p->cap, p->cap_err);
+        }
+        p->cap_built = true;
+    }
+    if (p->cap_rc != NEEDLE_OK) return fail(p->cap_rc, p->cap_err);
+    *reason = p->cap.reason;
+    *why = p->cap.why;
+    *prog = nullptr;
+    if (p->cap.reason != CAP_OK) return NEEDLE_OK;
+    if (!p->cap_lowered[cw - 1]) {
+        p->cap_prog[cw - 1] = lower_captures(p->cap, cw);
+        p->cap_lowered[cw - 1] = true;
+    }
+    if (!p->cap_prog[cw - 1].ok) {
+        *reason = CAP_TOO_BIG;
+        *why = "the capture program and two waves' slot files do not fit the LDS";
+        return NEEDLE_OK;
+    }
+    *prog = &p->cap_prog[cw - 1];
+    return NEEDLE_OK;
+}
+
+int needle_pattern_captures_info(const needle_pattern *cp, int char_width, needle_captures_info *o) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    if (!p || !o) return fail(NEEDLE_ERR_INVALID, "captures_info: NULL argument");
+    if (char_width != 1 && char_width != 2) return fail(NEEDLE_ERR_INVALID, "captures_info: char_width must be 1 or 2");
+    const CapProgram *prog = nullptr;
+    int reason = 0;
+    std::string why;
+    if (int rc = captures_program(p, char_width, &prog, &reason, &why)) return rc;
+    memset(o, 0, sizeof(*o));
+    o->available = reason == CAP_OK;
+    o->reason = reason;
+    o->n_groups = p->cap.n_groups;
+    if (reason == CAP_OK) {
+        o->n_states = p->cap.n_states;
+        o->n_cols = p->cap.n_cols;
+        o->max_threads = p->cap.max_threads;
+        o->n_slots = p->cap.n_slots;
+        o->n_op_lists = p->cap.n_op_lists;
+        o->n_ops = (int32_t)(p->cap.ops.size() / 2);
+        o->start = p->cap.start;
+        o->init_op = p->cap.init_op;
+        o->lds_bytes = (int32_t)prog->hdr.lds_bytes;
+    }
+    return NEEDLE_OK;
+}
+
+int needle_pattern_captures_tables(const needle_pattern *cp, int char_width, uint8_t *class_map, int32_t *next, int32_t *op_id, size_t table_cap,
+                                   int32_t *op_off, size_t op_off_cap, int32_t *ops, size_t ops_cap, int32_t *fin, size_t fin_cap) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    if (!p) return fail(NEEDLE_ERR_INVALID, "captures_tables: pattern is NULL");
+    if (char_width != 1 && char_width != 2) return fail(NEEDLE_ERR_INVALID, "captures_tables: char_width must be 1 or 2");
+    const CapProgram *prog = nullptr;
+    int reason = 0;
+    std::string why;
+    if (int rc = captures_program(p, char_width, &prog, &reason, &why)) return rc;
+    if (reason != CAP_OK) return fail(NEEDLE_ERR_UNSUPPORTED, std::string(kCapReasonNames[reason]) + ": " + why);
+    const CapTables &t = p->cap;
+    if (class_map) memcpy(class_map, t.class_map.data(), 65536);
+    auto put = [](int32_t *dst, size_t cap, const std::vector<int32_t> &src) {
+        if (!dst) return true;
+        if (cap < src.size()) return false;
+        if (!src.empty()) memcpy(dst, src.data(), src.size() * 4);
+        return true;
+    };
+    if (!put(next, table_cap, t.next) || !put(op_id, table_cap, t.op_id)) return fail(NEEDLE_ERR_INVALID, "captures_tables: table buffer too small");
+    if (!put(op_off, op_off_cap, t.op_off)) return fail(NEEDLE_ERR_INVALID, "captures_tables: op_off buffer too small");
+    if (!put(ops, ops_cap, t.ops)) return fail(NEEDLE_ERR_INVALID, "captures_tables: ops buffer too small");
+    if (!put(fin, fin_cap, t.fin)) return fail(NEEDLE_ERR_INVALID, "captures_tables: fin buffer too small");
+    return NEEDLE_OK;
+}
+
+// The groups of each span of a CSR span list (needle_captures_spans.h): a pure function of (text, list, pattern).
+int needle_captures_spans_packed_dev(const needle_pattern *cp, const needle_packed_view *v, const uint64_t *d_span_offsets, const int32_t *d_start,
+                                     const int32_t *d_end, int32_t *d_group_start, int32_t *d_group_end, uint64_t plane_stride, void *stream_) {
+    needle_pattern *p = const_cast<needle_pattern *>(cp);
+    if (!p) return fail(NEEDLE_ERR_INVALID, "pattern is NULL");
+    int rc = check_packed(v);
+    if (rc) return rc;
+    if (!d_span_offsets) return fail(NEEDLE_ERR_INVALID, "span offsets is NULL");
+    if ((d_start == nullptr) != (d_end == nullptr)) return fail(NEEDLE_ERR_INVALID, "one of start / end is NULL without the other");
+    if (d_start && (!d_group_start || !d_group_end)) return fail(NEEDLE_ERR_INVALID, "group planes are NULL with a span list");
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    const int cw = (int)v->char_width;
+    const CapProgram *prog = nullptr;
+    int reason = 0;
+    std::string why;
+    if ((rc = captures_program(p, cw, &prog, &reason, &why))) return rc;
+    if (reason != CAP_OK) return fail(NEEDLE_ERR_UNSUPPORTED, std::string(kCapReasonNames[reason]) + ": " + why);
+    if (v->n_rows == 0 || !d_start) return NEEDLE_OK; // (no rows, or no spans at all)
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const uint8_t *d_blob = nullptr;
+    int n_cus = 0;
+    {
+        std::lock_guard<std::mutex> lk(p->cap_mu);
+        if (!p->cap_cus.count(dev)) {
+            hipDeviceProp_t prop;
+            HIP_TRY(hipGetDeviceProperties(&prop, dev));
+            p->cap_cus[dev] = prop.multiProcessorCount;
+        }
+        n_cus = p->cap_cus[dev];
+        auto it = p->cap_resident.find(std::make_pair(dev, cw));
+        if (it == p->cap_resident.end()) {
+            uint8_t *d = nullptr;
+            HIP_TRY(hipMalloc((void **)&d, prog->blob.size()));
+            if (hipError_t ce = hipMemcpy(d, prog->blob.data(), prog->blob.size(), hipMemcpyHostToDevice); ce != hipSuccess) {
+                (void)hipFree(d);
+                return hip_fail(ce, "hipMemcpy(capture program)");
+            }
+            it = p->cap_resident.emplace(std::make_pair(dev, cw), d).first;
+        }
+        d_blob = it->second;
+    }
+    CapSpansArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = (const uint8_t *)v->data;
+    a.offsets = v->offsets;
+    a.n_rows = v->n_rows;
+    a.prog = d_blob;
+    a.hdr = prog->hdr;
+    a.span_off = d_span_offsets;
+    a.start = d_start;
+    a.end = d_end;
+    a.gstart = d_group_start;
+    a.gend = d_group_end;
+    a.plane_stride = plane_stride;
+    HIP_TRY(launch_captures_spans(cw, a, n_cus, (hipStream_t)stream_));
     return NEEDLE_OK;
 }
 

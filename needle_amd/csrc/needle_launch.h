@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <functional>
+#include "needle_captures.h"
 #include "needle_device.h"
 #include "needle_find_all.h"
 #include "needle_gather.h"
@@ -30,6 +31,8 @@ bool packed_find_all_lane_shape(uint32_t prog_lds_bytes, int char_width, int *wa
 hipError_t launch_packed_set(int op, int char_width, const PackedSetArgs &a, int n_cus, hipStream_t stream);
 // needle_set_spans2.hip: a pattern set's group on a CSR span list of packed rows (needle_set_spans.h): which members match each span
 hipError_t launch_set_spans(int char_width, const SetSpansArgs &a, int n_cus, hipStream_t stream);
+// needle_captures_spans2.hip: the capturing groups of each span of a CSR span list of packed rows (needle_captures_spans.h)
+hipError_t launch_captures_spans(int char_width, const CapSpansArgs &a, int n_cus, hipStream_t stream);
 // needle_compact.hip
 int compact_blocked16(uint64_t n, uint32_t max_per_row, uint64_t *d_offsets, uint32_t *d_start_end16, uint64_t cap, uint64_t *d_total, hipStream_t stream,
                       const std::function<int(uint32_t *counts, uint32_t *blocks)> &fill);

@@ -93,7 +93,7 @@ struct JOrderLite {
 };
 
 // ------------------------------------------------------------------------------------------------ AST
-enum Kind { K_LITERAL, K_RANGE, K_CONCAT, K_UNION, K_REP, K_COUNTED, K_LPAREN };
+enum Kind { K_LITERAL, K_RANGE, K_CONCAT, K_UNION, K_REP, K_COUNTED, K_LPAREN, K_GROUP };
 struct Node;
 using NodeP = std::shared_ptr<Node>;
 struct Node {
@@ -103,6 +103,7 @@ struct Node {
     NodeP a, b;         // concat: head/tail; union: left/right; rep/counted: a
     bool with_priority = false;
     int min = 0, max = 0;
+    int group = -1;     // keep-groups parse only: K_LPAREN / K_GROUP: the capturing group's number (1 ..), -1 = not capturing
 };
 NodeP mk(Kind k) { auto n = std::make_shared<Node>(); n->kind = k; return n; }
 NodeP lit(const std::u16string &s) { auto n = mk(K_LITERAL); n->lit = s; return n; }
@@ -227,12 +228,15 @@ NodeP reversed(const NodeP &n) {
 // ------------------------------------------------------------------------------------------------ parser
 class Parser {
   public:
-    Parser(const std::u16string &r, int flags) : re(r) {
+    // keep_groups: the second parse of the capture program (needle_captures.h) -- what collapse_paren pushes is wrapped in a
+    // K_GROUP node carrying the number of its opening parenthesis.  Off (compile_regex): the parse is what it always was.
+    Parser(const std::u16string &r, int flags, bool keep_groups_ = false) : re(r), keep_groups(keep_groups_) {
         dot_all = flags & NEEDLE_DOTALL;
         ci = flags & NEEDLE_CASE_INSENSITIVE;
         ucc = flags & NEEDLE_UNICODE_CHARACTER_CLASS;
         uci = ucc ? true : (flags & NEEDLE_UNICODE_CASE) != 0;
     }
+    int group_count() const { return n_groups; }
     NodeP parse() {
         while (idx < re.size()) {
             const char16_t c = take();
@@ -246,7 +250,10 @@ class Parser {
             case u'(':
                 push(mk(K_LPAREN));
                 if (peek_str(u"?:")) { take(); take(); }
-                else if (peek_str(u"?<")) consume_named_group();
+                else {
+                    if (keep_groups) nodes.back()->group = ++n_groups;
+                    if (peek_str(u"?<")) consume_named_group();
+                }
                 break;
             case u'{': {
                 if (nodes.empty()) throw err("Found '{' with no preceding regex");
@@ -315,6 +322,8 @@ class Parser {
     const std::u16string &re;
     size_t idx = 0;
     bool dot_all, ci, uci, ucc;
+    bool keep_groups;
+    int n_groups = 0;
     std::vector<NodeP> nodes;
 
     SyntaxError err(const std::string &m) { return SyntaxError(m + ". Regex index=" + std::to_string(idx)); }
@@ -410,17 +419,23 @@ class Parser {
                 if (prev->a && prev->b) { node = concat_nodes(prev, node); continue; }
                 if (nodes.empty()) throw err("found '|' with no preceding content");
                 if (nodes.back()->kind == K_LPAREN) {
+                    const int g = nodes.back()->group;
                     nodes.pop_back();
-                    push(make_union(prev->a, node, true));
+                    push(wrap_group(make_union(prev->a, node, true), g));
                     return;
                 }
                 node = make_union(prev->a, node, true);
             } else node = concatenate(prev, node);
             if (nodes.empty()) throw err("found unbalanced ')'");
         }
+        const int g = nodes.back()->group;
         nodes.pop_back();
         if (!node) node = lit(u"");
-        push(node);
+        push(wrap_group(node, g));
+    }
+    static NodeP wrap_group(const NodeP &body, int g) { // (g < 0: not capturing, or not the keep-groups parse)
+        if (g < 0) return body;
+        auto n = mk(K_GROUP); n->a = body; n->group = g; return n;
     }
     int consume_int() { // :535-551
         const size_t start = idx;
@@ -1351,7 +1366,123 @@ Dfa build(const std::vector<Instr> &prog, ConvMode mode) { // NFAToDFACompiler.c
     return m;
 }
 
+// ------------------------------------------------------------------------------------------------ capture program (needle_captures.h)
+// The priority Thompson program of the keep-groups parse: SPLIT prefers x, `+` is x x* (as the parser makes it), {m,n} is m copies and
+// n - m nested optionals, a union of single chars and ranges is ONE char-set instruction (no group inside: its order decides nothing).
+bool cap_charset(const NodeP &n, std::vector<std::pair<int, int>> &out) {
+    if (!n) return false;
+    if (n->kind == K_RANGE) { out.emplace_back(n->range.start, n->range.end); return true; }
+    if (n->kind == K_LITERAL && n->lit.size() == 1) { out.emplace_back(n->lit[0], n->lit[0]); return true; }
+    if (n->kind == K_UNION) return cap_charset(n->a, out) && cap_charset(n->b, out);
+    return false;
+}
+bool cap_nullable(const NodeP &n) {
+    switch (n->kind) {
+    case K_LITERAL: return n->lit.empty();
+    case K_RANGE: return false;
+    case K_CONCAT: return cap_nullable(n->a) && cap_nullable(n->b);
+    case K_UNION: if (!n->b) throw CompileError("union with an empty branch"); return cap_nullable(n->a) || cap_nullable(n->b);
+    case K_REP: return true;
+    case K_COUNTED: return n->min == 0 || cap_nullable(n->a);
+    case K_GROUP: return cap_nullable(n->a);
+    default: throw CompileError("unexpected node");
+    }
+}
+bool cap_nullable_loop(const NodeP &n) { // some `*`, `+` or {m,n} with n > 1 whose body can match the empty string
+    switch (n->kind) {
+    case K_LITERAL: case K_RANGE: return false;
+    case K_CONCAT: case K_UNION: if (!n->b) throw CompileError("union with an empty branch"); return cap_nullable_loop(n->a) || cap_nullable_loop(n->b);
+    case K_REP: return cap_nullable(n->a) || cap_nullable_loop(n->a);
+    case K_COUNTED: return (n->max > 1 && cap_nullable(n->a)) || cap_nullable_loop(n->a);
+    case K_GROUP: return cap_nullable_loop(n->a);
+    default: throw CompileError("unexpected node");
+    }
+}
+struct CapBuilder {
+    std::vector<CapInstr> &v;
+    size_t max_instrs;
+    bool overflow = false;
+    int emit(int op, int x = -1, int y = -1) {
+        if (v.size() >= max_instrs) { overflow = true; throw CompileError("capture program too big"); }
+        CapInstr i; i.op = op; i.x = x; i.y = y;
+        v.push_back(std::move(i));
+        return (int)v.size() - 1;
+    }
+    void cset(std::vector<std::pair<int, int>> rs) {
+        std::sort(rs.begin(), rs.end());
+        std::vector<std::pair<int, int>> m;
+        for (const auto &r : rs) {
+            if (!m.empty() && r.first <= m.back().second + 1) m.back().second = std::max(m.back().second, r.second);
+            else m.push_back(r);
+        }
+        v[(size_t)emit(CAP_CSET)].ranges = std::move(m);
+    }
+    void node(const NodeP &n) {
+        std::vector<std::pair<int, int>> rs;
+        switch (n->kind) {
+        case K_LITERAL: for (char16_t c : n->lit) cset({{(int)c, (int)c}}); break;
+        case K_RANGE: cset({{n->range.start, n->range.end}}); break;
+        case K_CONCAT: node(n->a); node(n->b); break;
+        case K_UNION: {
+            if (!n->b) throw CompileError("union with an empty branch");
+            if (cap_charset(n, rs)) { cset(rs); break; }
+            const int sp = emit(CAP_SPLIT);
+            v[(size_t)sp].x = (int)v.size();
+            node(n->a);
+            const int j = emit(CAP_JMP);
+            v[(size_t)sp].y = (int)v.size();
+            node(n->b);
+            v[(size_t)j].x = (int)v.size();
+            break;
+        }
+        case K_REP: {
+            const int sp = emit(CAP_SPLIT);
+            v[(size_t)sp].x = (int)v.size();
+            node(n->a);
+            emit(CAP_JMP, sp);
+            v[(size_t)sp].y = (int)v.size();
+            break;
+        }
+        case K_COUNTED: {
+            for (int r = 0; r < n->min; ++r) node(n->a);
+            std::vector<int> sw;
+            for (int r = n->min; r < n->max; ++r) { sw.push_back(emit(CAP_SPLIT)); v[(size_t)sw.back()].x = (int)v.size(); node(n->a); }
+            for (int s : sw) v[(size_t)s].y = (int)v.size();
+            break;
+        }
+        case K_GROUP:
+            emit(CAP_SAVE, 2 * (n->group - 1));
+            node(n->a);
+            emit(CAP_SAVE, 2 * (n->group - 1) + 1);
+            break;
+        default: throw CompileError("Unhandled ast node type");
+        }
+    }
+};
+
 } // namespace
+
+int build_captures_nfa(const std::u16string &regex, int flags, size_t max_instrs, CapNfa &out, std::string &err) {
+    out = CapNfa();
+    CapBuilder b{out.prog, max_instrs};
+    try {
+        Parser parser(regex, flags, true);
+        NodeP ast = parser.parse();
+        out.n_groups = parser.group_count();
+        out.nullable_loop = cap_nullable_loop(ast);
+        if (out.nullable_loop) return NEEDLE_OK; // (refused: no program is built)
+        b.node(ast);
+        b.emit(CAP_MATCH);
+        return NEEDLE_OK;
+    } catch (const SyntaxError &e) {
+        err = std::string("PatternSyntaxException: ") + e.what();
+        return NEEDLE_ERR_SYNTAX;
+    } catch (const std::exception &e) {
+        if (b.overflow) { out.too_big = true; out.prog.clear(); return NEEDLE_OK; }
+        err = std::string("PatternClassCompilationException: ") + e.what();
+        return NEEDLE_ERR_COMPILE;
+    }
+}
 
 int compile_regex(const std::u16string &regex, int flags, RefTables &out, std::string &err) {
     try {

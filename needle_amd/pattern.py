@@ -1580,6 +1580,136 @@ class Pattern:
         off, st, en = self.find_all_utf8_packed(data, offsets)
         return [list(zip(st[off[i]:off[i + 1]].tolist(), en[off[i]:off[i + 1]].tolist())) for i in range(len(rows))]
 
+    # ---- capturing groups: the group spans of every span of a match list (needle_pattern_captures_*, needle_captures_spans_packed_dev)
+    def captures_info(self, char_width=1):
+        """needle_pattern_captures_info as a dict: available, reason (None | "NULLABLE_LOOP" | "NO_REGEX" | "TOO_MANY_GROUPS" | "TOO_BIG"),
+        n_groups, and for available programs n_states, n_cols, max_threads, n_slots, n_op_lists, n_ops, start, init_op, lds_bytes.  Needs no
+        device."""
+        o = _lib.CapturesInfo()
+        _check(_lib.lib().needle_pattern_captures_info(self._h, char_width, ctypes.byref(o)))
+        d = {k: getattr(o, k) for k, _ in o._fields_}
+        d["available"] = bool(o.available)
+        d["reason"] = _lib.CAPTURES_REASONS[o.reason]
+        return d
+
+    def group_count(self):
+        """The pattern's capturing groups, numbered by their opening parenthesis (patterns without regex text raise)."""
+        n = self.captures_info()["n_groups"]
+        if n < 0:
+            raise PatternException("the pattern has no regex text (from_tables / from_bytes): its groups are unknown")
+        return n
+
+    def captures_tables(self, char_width=1):
+        """needle_pattern_captures_tables as a dict of numpy arrays (class_map uint8[65536], next / op_id int32[n_states, n_cols], op_off,
+        ops int32[n_ops, 2] = (dst, src), fin) with captures_info's numbers beside them: the tagged automaton, to be walked on the CPU."""
+        info = self.captures_info(char_width)
+        cells = info["n_states"] * info["n_cols"]
+        t = dict(info, class_map=np.zeros(65536, np.uint8), next=np.zeros(cells, np.int32), op_id=np.zeros(cells, np.int32),
+                 op_off=np.zeros(info["n_op_lists"] + 1, np.int32), ops=np.zeros(2 * info["n_ops"], np.int32), fin=np.zeros(info["n_states"], np.int32))
+        _check(_lib.lib().needle_pattern_captures_tables(self._h, char_width, t["class_map"].ctypes.data, t["next"].ctypes.data, t["op_id"].ctypes.data, cells,
+                                                         t["op_off"].ctypes.data, t["op_off"].size, t["ops"].ctypes.data, t["ops"].size,
+                                                         t["fin"].ctypes.data, t["fin"].size))
+        t["next"], t["op_id"], t["ops"] = t["next"].reshape(info["n_states"], -1), t["op_id"].reshape(info["n_states"], -1), t["ops"].reshape(-1, 2)
+        return t
+
+    def captures_spans_packed(self, data, offsets, span_offsets, start, end, stream=None, out=None):
+        """needle_captures_spans_packed_dev: the capturing groups of each span of a CSR span list over packed rows -> (gstart, gend), int32
+        device tensors [G + 1, M] indexed like `start` in their second dimension: row g holds group g of a full match of row[start:end]
+        (group 0 the clamped span itself), -1 everywhere where the pattern does not match that text whole, (-1, -1) for a group the match
+        did not pass.  span_offsets int64[n_rows + 1], start / end int32 -- what find_all_packed returns; spans are clamped into their rows
+        and need not be monotone or disjoint; columns below span_offsets[0] are untouched.  out: a caller-owned pair of such tensors
+        (second dimension at least M).  Stream-ordered, no host synchronisation.  numpy inputs are uploaded and the planes brought back."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            d, (o, so, st, en) = Pattern._gather_host_args(data, ((offsets, np.int64), (span_offsets, np.int64), (start, np.int32), (end, np.int32)))
+            gs, ge = self.captures_spans_packed(d, o, so, st, en, stream)
+            return gs.cpu().numpy(), ge.cpu().numpy()
+        Pattern._gather_check(data, ((offsets, torch.int64, "offsets"), (span_offsets, torch.int64, "span_offsets"), (start, torch.int32, "start"),
+                                     (end, torch.int32, "end")))
+        n, dv, m = offsets.numel() - 1, data.device, start.numel()
+        assert n >= 0 and span_offsets.numel() == n + 1 and end.numel() == m, "span_offsets: n_rows + 1 entries; start / end alike"
+        planes = self.group_count() + 1
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        with torch.cuda.device(dv):
+            s = torch.cuda.current_stream(dv).cuda_stream if stream is None else stream
+            if out is not None:
+                gs, ge = out
+                for t in (gs, ge):
+                    assert t.device == dv and t.dtype == torch.int32 and t.dim() == 2 and t.is_contiguous() and t.size(0) == planes and t.size(1) >= m
+                assert gs.size(1) == ge.size(1)
+            else:
+                gs = torch.empty((planes, m), dtype=torch.int32, device=dv)
+                ge = torch.empty((planes, m), dtype=torch.int32, device=dv)
+            some = m > 0
+            _check(L.needle_captures_spans_packed_dev(self._h, ctypes.byref(v), span_offsets.data_ptr(), start.data_ptr() if some else None,
+                                                      end.data_ptr() if some else None, gs.data_ptr() if some else None,
+                                                      ge.data_ptr() if some else None, gs.size(1), s))
+        return gs, ge
+
+    def find_all_groups_packed(self, data, offsets, stream=None):
+        """Every non-overlapping match of every packed row with its groups -> (match_offsets int64[n_rows + 1], gstart, gend int32[G + 1, m]):
+        find_all_packed, then captures_spans_packed on its list, on one stream; row 0 of the planes is the match list itself.  numpy inputs
+        are uploaded and the results brought back."""
+        if isinstance(data, np.ndarray):
+            d, (o,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+            off, gs, ge = self.find_all_groups_packed(d, o, stream)
+            return off.cpu().numpy(), gs.cpu().numpy(), ge.cpu().numpy()
+        off, st, en = self.find_all_packed(data, offsets, stream)
+        gs, ge = self.captures_spans_packed(data, offsets, off, st, en, stream)
+        return off, gs, ge
+
+    def extract_group_packed(self, data, offsets, g, stream=None):
+        """Group g of every match of every packed row as a NEW packed batch -> (out_data, out_offsets, match_offsets): find_all_groups_packed,
+        then gather_spans_packed on plane g.  A group the match did not pass, (-1, -1), clamps to an empty row."""
+        host = isinstance(data, np.ndarray)
+        if host:
+            data, (offsets,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+        off, gs, ge = self.find_all_groups_packed(data, offsets, stream)
+        assert 0 <= g < gs.size(0), "group out of range"
+        text, toff = Pattern.gather_spans_packed(data, offsets, off, gs[g].contiguous(), ge[g].contiguous(), stream)
+        if host:
+            return Pattern._gather_host_text(text), toff.cpu().numpy(), off.cpu().numpy()
+        return text, toff, off
+
+    def find_all_groups_strings(self, strings):
+        """Every match of every str (UTF-16 code units) with its groups -> per string a list of matches, each a list of (start, end) for
+        groups 0 .. G, None for a group the match did not pass (re.finditer's m.span(g), pack_strings + find_all_groups_packed)."""
+        data, offsets = pack_strings(strings)
+        off, gs, ge = self.find_all_groups_packed(data, offsets)
+        return Pattern._groups_rows(off, gs, ge, len(strings))
+
+    @staticmethod
+    def _groups_rows(off, gs, ge, n):
+        span = lambda s, e: None if s < 0 else (s, e)
+        return [[[span(int(gs[g, m]), int(ge[g, m])) for g in range(gs.shape[0])] for m in range(int(off[i]), int(off[i + 1]))] for i in range(n)]
+
+    def find_all_groups_utf8_packed(self, data, offsets, stream=None):
+        """Every match of every UTF-8 packed row with its groups, as BYTE offsets into the rows -> (match_offsets, gstart, gend int32[G + 1, m]):
+        utf16_from_utf8_packed, find_all_groups_packed on the UTF-16 batch, then utf8_positions_packed on every plane (-1 stays -1), one
+        stream.  numpy inputs are uploaded and the results brought back."""
+        import torch
+        data, offsets, host = Pattern._utf8_dev(data, offsets)
+        one = torch.cuda.current_stream(data.device) if stream is None else torch.cuda.ExternalStream(stream, device=data.device)
+        with torch.cuda.device(data.device), torch.cuda.stream(one):
+            s = one.cuda_stream
+            units, uoff, _, _ = Pattern.utf16_from_utf8_packed(data, offsets, stream=s)
+            moff, gs, ge = self.find_all_groups_packed(units, uoff, stream=s)
+            bs, be = torch.empty_like(gs), torch.empty_like(ge)
+            for g in range(gs.size(0)):
+                Pattern.utf8_positions_packed(data, offsets, moff, gs[g], stream=s, out=bs[g])
+                Pattern.utf8_positions_packed(data, offsets, moff, ge[g], stream=s, out=be[g])
+        if host:
+            return moff.cpu().numpy(), bs.cpu().numpy(), be.cpu().numpy()
+        return moff, bs, be
+
+    def find_all_groups_bytes(self, rows):
+        """find_all_groups_strings for UTF-8 `bytes` rows: byte offsets (pack_bytes + find_all_groups_utf8_packed)."""
+        data, offsets = pack_bytes(rows)
+        off, gs, ge = self.find_all_groups_utf8_packed(data, offsets)
+        return Pattern._groups_rows(off, gs, ge, len(rows))
+
     def replace_all_bytes(self, rows, repl):
         """Every match of every UTF-8 `bytes` row replaced by the bytes `repl` -> list[bytes]: find_all_utf8_packed on the device, then
         splice_packed at char width 1 on the ORIGINAL bytes with the replacement's bytes -- no encoder back to UTF-8 is involved, and the

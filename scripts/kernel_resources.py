@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPRs / scratch of every instantiation of the tiled scan kernel, of the per-lane and the lock-step find-all kernels of fixed-stride
 rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (transducer and per-lane), of the packed-rows pattern-set kernel,
-of the pattern-set kernel of span lists (needle_set_spans.h) and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
+of the pattern-set kernel of span lists (needle_set_spans.h), of the capture kernel of span lists (needle_captures_spans.h) and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
 (needle_replace.hip, needle_replace_each.hip: 4 waves per workgroup, static LDS) and of the gather kernels (needle_gather.hip: the same) and of the UTF-8 kernels (needle_utf8.hip: the same)
 and of the line-splitting kernels (needle_lines.hip: one workgroup of 256 lanes per tile, static LDS)
 (cross-compiled here, no
@@ -20,7 +20,7 @@ for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", 
            "needle_packed_matches", "needle_packed_contained", "needle_packed_find1", "needle_packed_find2", "needle_packed_next1",
            "needle_packed_next2", "needle_packed_forms1", "needle_packed_forms2",
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
-           "needle_packed_set1", "needle_packed_set2", "needle_set_spans1", "needle_set_spans2",
+           "needle_packed_set1", "needle_packed_set2", "needle_set_spans1", "needle_set_spans2", "needle_captures_spans1", "needle_captures_spans2",
            "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2",
            "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace", "needle_replace_each", "needle_gather", "needle_utf8", "needle_lines"):
     out = os.path.join(tmp, tu + ".s")
@@ -90,6 +90,12 @@ for k, sc, v in sorted(rows):
     m = re.search(r"set_spans_kernelILi(\d)ELi(\d)E", k)
     if m:
         print("%4d %4d  span masks  cw%s %-8s offsets %5d B" % (sc, v, m.group(1), modes[m.group(2)], 2 * 65 * 8))
+# the capture kernel of span lists (needle_captures_spans.h): LDS = program + per wave 1040 bytes of offsets and 256 bytes per slot, sized at launch
+print("capture span kernels (needle_captures_spans.h): scratch bytes / VGPRs / kernel / LDS per wave")
+for k, sc, v in sorted(rows):
+    m = re.search(r"captures_spans_kernelILi(\d)E", k)
+    if m:
+        print("%4d %4d  group spans cw%s offsets %5d B + 256 B per slot" % (sc, v, m.group(1), 2 * 65 * 8))
 # the n-gram filter kernels (needle_ngram_kernel.h): LDS = program + bitmaps + per wave the queues and slots (packed rows: + the row starts)
 names_ng = dict(names, **{"3": "find-all"})
 for title, rx in (("n-gram filter kernels, fixed-stride rows (needle_ngram.hip): scratch bytes / VGPRs / kernel", r"ngram_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d)ELb(\d)ELb(\d)E"),
