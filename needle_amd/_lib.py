@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("NEEDLE_LIB", os.path.join(_HERE, "libneedle_hip.so"))
 NEEDLE_OK, ERR_INVALID, ERR_SYNTAX, ERR_COMPILE, ERR_UNSUPPORTED, ERR_DEVICE = 0, 1, 2, 3, 4, 5
 REPLACE_MAX_UNITS = 4096  # NEEDLE_REPLACE_MAX_UNITS
 REPLACE_MAX_CHOICES = 256  # NEEDLE_REPLACE_MAX_CHOICES
+TEMPLATE_MAX_REFS = 16  # NEEDLE_TEMPLATE_MAX_REFS
 CHOICE_INDEX, CHOICE_LOWEST_BIT = 0, 1  # NEEDLE_CHOICE_INDEX, NEEDLE_CHOICE_LOWEST_BIT
 GATHER_MATCHES, GATHER_PIECES = 0, 1  # NEEDLE_GATHER_MATCHES, NEEDLE_GATHER_PIECES
 UTF8_MAX_EXPANSION = 1  # NEEDLE_UTF8_MAX_EXPANSION: units(row) <= bytes(row)
@@ -29,6 +30,7 @@ EXPORTS = [
     "needle_find_packed8_packed_dev", "needle_find_packed16_packed_host", "needle_find_packed8_packed_host",
     "needle_replace_all_lengths_packed_dev", "needle_replace_all_fill_packed_dev", "needle_replace_all_packed_host",
     "needle_replace_each_lengths_packed_dev", "needle_replace_each_fill_packed_dev", "needle_set_replace_each_packed_host",
+    "needle_template_parse", "needle_replace_groups_lengths_packed_dev", "needle_replace_groups_fill_packed_dev",
     "needle_gather_spans_lengths_packed_dev", "needle_gather_spans_fill_packed_dev", "needle_split_spans_packed_dev", "needle_gather_chunk_spans",
     "needle_gather_matches_packed_host",
     "needle_utf16_lengths_from_utf8_packed_dev", "needle_utf16_from_utf8_packed_dev", "needle_utf8_positions_packed_dev", "needle_utf8_window_bytes",
@@ -93,6 +95,11 @@ class PrefilterInfo2(ctypes.Structure):
 class SetInfo(ctypes.Structure):
     _fields_ = ([("n_patterns", ctypes.c_int32), ("n_groups", ctypes.c_int32)] +
                 [(k, ctypes.c_int32 * 32) for k in ("first_pattern", "pattern_count", "n_states", "n_columns", "kernel_mode", "lds_bytes")])
+
+
+class Template(ctypes.Structure):
+    """needle_template: a parsed replacement template, all host memory."""
+    _fields_ = [("n_refs", ctypes.c_uint32), ("groups", ctypes.c_void_p), ("lit_offsets", ctypes.c_void_p), ("lits", ctypes.c_void_p)]
 
 
 class CapturesInfo(ctypes.Structure):
@@ -188,6 +195,10 @@ def lib():
     L.needle_replace_each_lengths_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, I, VP, ctypes.c_uint32, VP, VP]
     L.needle_replace_each_fill_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, I, VP, VP, ctypes.c_uint32, VP, VP, VP]
     L.needle_set_replace_each_packed_host.argtypes = [VP, VP, P(PackedView), VP, VP, ctypes.c_uint32, VP, VP, ctypes.c_uint64, P(ctypes.c_uint64)]
+    U32 = ctypes.c_uint32
+    L.needle_template_parse.argtypes = [VP, ctypes.c_size_t, U32, VP, U32, VP, U32, VP, U32, P(U32), P(U32)]
+    L.needle_replace_groups_lengths_packed_dev.argtypes = [P(PackedView), VP, VP, VP, ctypes.c_uint64, U32, P(Template), VP, VP]
+    L.needle_replace_groups_fill_packed_dev.argtypes = [P(PackedView), VP, VP, VP, ctypes.c_uint64, U32, P(Template), VP, VP, VP]
     L.needle_gather_spans_lengths_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, VP]
     L.needle_gather_spans_fill_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, VP, VP]
     L.needle_split_spans_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP, VP, VP, VP]

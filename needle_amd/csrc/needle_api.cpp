@@ -23,6 +23,7 @@
 #include "needle_lower.h"
 #include "needle_regex.h"
 #include "needle_set.h"
+#include "needle_template.h"
 
 using namespace needle;
 
@@ -1655,6 +1656,120 @@ int needle_replace_each_fill_packed_dev(const needle_packed_view *v, const uint6
     if (e == hipSuccess) e = launch_replace_each_fill(a, cus, stream);
     if (d_table) (void)scratch_free(d_table, stream);
     return e == hipSuccess ? NEEDLE_OK : hip_fail(e, "needle_replace_each_fill_packed_dev");
+}
+
+// A replacement template into its canonical form (needle_template.h): host code, no device.
+int needle_template_parse(const uint16_t *tmpl, size_t n_units, uint32_t n_groups, int32_t *groups, uint32_t groups_cap, uint32_t *lit_offsets,
+                          uint32_t lit_offsets_cap, uint16_t *lits, uint32_t lits_cap, uint32_t *n_refs, uint32_t *n_lit_units) {
+    if (!tmpl && n_units) return fail(NEEDLE_ERR_INVALID, "template is NULL");
+    if ((!groups && groups_cap) || (!lit_offsets && lit_offsets_cap) || (!lits && lits_cap))
+        return fail(NEEDLE_ERR_INVALID, "a NULL output has capacity 0");
+    TemplateForm f;
+    std::string err;
+    if (!template_parse(tmpl, n_units, n_groups, &f, &err)) return fail(NEEDLE_ERR_INVALID, err);
+    if (n_refs) *n_refs = (uint32_t)f.groups.size();
+    if (n_lit_units) *n_lit_units = (uint32_t)f.lits.size();
+    if ((groups && groups_cap < f.groups.size()) || (lit_offsets && lit_offsets_cap < f.lit_offsets.size()) || (lits && lits_cap < f.lits.size()))
+        return fail(NEEDLE_ERR_INVALID, "an output's capacity is below the parsed template's size (call with NULL outputs to size it)");
+    if (groups && !f.groups.empty()) memcpy(groups, f.groups.data(), f.groups.size() * sizeof(int32_t));
+    if (lit_offsets) memcpy(lit_offsets, f.lit_offsets.data(), f.lit_offsets.size() * sizeof(uint32_t));
+    if (lits && !f.lits.empty()) memcpy(lits, f.lits.data(), f.lits.size() * sizeof(uint16_t));
+    return NEEDLE_OK;
+}
+
+// The splice with a template of literals and group references (needle_replace_groups.hip): the checks of replace_args, then the
+// planes' and the template's; *table is what the put kernel takes to the device -- the head (the references' groups, a replaced
+// match's pieces in output order) and, with_lits, the literals' units behind it.
+static int replace_groups_args(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_group_start, const int32_t *d_group_end,
+                               uint64_t plane_stride, uint32_t n_planes, const needle_template *t, bool with_lits, ReplaceGroupsArgs *a,
+                               std::vector<uint8_t> *table) {
+    ReplaceArgs plain;
+    int rc = replace_args(v, d_match_offsets, d_group_start, d_group_end, 0, &plain);
+    if (rc) return rc;
+    if (n_planes == 0) return fail(NEEDLE_ERR_INVALID, "n_planes is 0: plane 0 is the match itself");
+    if (!t) return fail(NEEDLE_ERR_INVALID, "template is NULL");
+    if (!t->lit_offsets) return fail(NEEDLE_ERR_INVALID, "template literal offsets is NULL");
+    if (t->n_refs > NEEDLE_TEMPLATE_MAX_REFS) return fail(NEEDLE_ERR_INVALID, "more than NEEDLE_TEMPLATE_MAX_REFS group references");
+    if (t->n_refs && !t->groups) return fail(NEEDLE_ERR_INVALID, "template groups is NULL");
+    const uint32_t K = t->n_refs;
+    for (uint32_t k = 0; k < K; ++k)
+        if (t->groups[k] < 0 || (uint32_t)t->groups[k] >= n_planes)
+            return fail(NEEDLE_ERR_INVALID, "template reference " + std::to_string(k) + " names group " + std::to_string(t->groups[k]) + ": outside 0 .. n_planes - 1");
+    if (t->lit_offsets[0] != 0) return fail(NEEDLE_ERR_INVALID, "template literal offsets must start at 0");
+    for (uint32_t i = 0; i <= K; ++i)
+        if (t->lit_offsets[i + 1] < t->lit_offsets[i]) return fail(NEEDLE_ERR_INVALID, "template literal offsets decrease");
+    const uint32_t units = t->lit_offsets[K + 1];
+    if (units > NEEDLE_REPLACE_MAX_UNITS) return fail(NEEDLE_ERR_INVALID, "template literals longer than NEEDLE_REPLACE_MAX_UNITS code units");
+    if (with_lits && units && !t->lits) return fail(NEEDLE_ERR_INVALID, "template literals is NULL");
+    const uint32_t cw = plain.cw, unit_bytes = with_lits ? units * cw : 0u;
+    table->assign(kGroupsHeadBytes + ((unit_bytes + 15u) & ~15u), 0);
+    uint32_t *head = (uint32_t *)table->data();
+    uint32_t pieces = 0;
+    for (uint32_t i = 0; i <= K; ++i) {
+        const uint32_t lo = t->lit_offsets[i], len = t->lit_offsets[i + 1] - lo;
+        if (len) head[kGroupsPieceWord0 + pieces++] = (lo * cw) | ((len * cw) << 14); // (an empty literal is no piece)
+        if (i < K) {
+            head[i] = (uint32_t)t->groups[i];
+            head[kGroupsPieceWord0 + pieces++] = kGroupsRef | (uint32_t)t->groups[i];
+        }
+    }
+    if (unit_bytes) memcpy(table->data() + kGroupsHeadBytes, t->lits, unit_bytes);
+    memset(a, 0, sizeof(*a));
+    a->data = plain.data;
+    a->in_off = plain.in_off;
+    a->n_rows = plain.n_rows;
+    a->cw = cw;
+    a->n_refs = K;
+    a->lit_units = units;
+    a->pieces = pieces + 1u; // (and the gap behind the match)
+    a->chunk = kGroupsTableEntries / a->pieces;
+    a->inv_pieces = (65536u + a->pieces - 1u) / a->pieces;
+    a->match_off = d_match_offsets;
+    a->gstart = d_group_start;
+    a->gend = d_group_end;
+    a->plane_stride = plane_stride;
+    return NEEDLE_OK;
+}
+
+static int replace_groups_run(ReplaceGroupsArgs &a, const std::vector<uint8_t> &table, bool fill, hipStream_t stream, const char *what) {
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    uint8_t *d_table = nullptr;
+    hipError_t e = scratch_malloc((void **)&d_table, table.size(), stream);
+    if (e == hipSuccess) e = launch_replace_put(table.data(), (uint32_t)table.size(), d_table, stream);
+    a.table = d_table;
+    if (e == hipSuccess) e = fill ? launch_replace_groups_fill(a, cus, stream) : launch_replace_groups_lengths(a, cus, stream);
+    if (d_table) (void)scratch_free(d_table, stream);
+    return e == hipSuccess ? NEEDLE_OK : hip_fail(e, what);
+}
+
+int needle_replace_groups_lengths_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_group_start,
+                                             const int32_t *d_group_end, uint64_t plane_stride, uint32_t n_planes, const needle_template *tmpl,
+                                             uint64_t *d_out_lengths, void *stream_) {
+    ReplaceGroupsArgs a;
+    std::vector<uint8_t> table;
+    int rc = replace_groups_args(v, d_match_offsets, d_group_start, d_group_end, plane_stride, n_planes, tmpl, false, &a, &table);
+    if (rc) return rc;
+    if (!d_out_lengths) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    a.out_len = d_out_lengths;
+    return replace_groups_run(a, table, false, (hipStream_t)stream_, "needle_replace_groups_lengths_packed_dev");
+}
+
+int needle_replace_groups_fill_packed_dev(const needle_packed_view *v, const uint64_t *d_match_offsets, const int32_t *d_group_start,
+                                          const int32_t *d_group_end, uint64_t plane_stride, uint32_t n_planes, const needle_template *tmpl,
+                                          const uint64_t *d_out_offsets, void *d_out_data, void *stream_) {
+    ReplaceGroupsArgs a;
+    std::vector<uint8_t> table;
+    int rc = replace_groups_args(v, d_match_offsets, d_group_start, d_group_end, plane_stride, n_planes, tmpl, true, &a, &table);
+    if (rc) return rc;
+    if (!d_out_offsets || !d_out_data) return fail(NEEDLE_ERR_INVALID, "output offsets / buffer is NULL");
+    if (((uintptr_t)d_out_data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "output data must be 4-byte aligned");
+    if (v->n_rows == 0) return NEEDLE_OK;
+    a.out_off = d_out_offsets;
+    a.out = (uint8_t *)d_out_data;
+    return replace_groups_run(a, table, true, (hipStream_t)stream_, "needle_replace_groups_fill_packed_dev");
 }
 
 // Spans of packed rows as a new packed batch (needle_gather.hip): pure functions of (text, span list) -- no pattern, no route.  The checks

@@ -13,6 +13,7 @@
 #include "needle_ngram.h"
 #include "needle_replace.h"
 #include "needle_replace_each.h"
+#include "needle_replace_groups.h"
 
 namespace needle {
 
@@ -84,6 +85,9 @@ hipError_t launch_replace_fill(const ReplaceArgs &a, int n_cus, hipStream_t stre
 // needle_replace_each.hip: the splice with a replacement per match out of a table (needle_replace_each_*_packed_dev)
 hipError_t launch_replace_each_lengths(const ReplaceEachArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_replace_each_fill(const ReplaceEachArgs &a, int n_cus, hipStream_t stream);
+// needle_replace_groups.hip: the splice with a template of literals and group references (needle_replace_groups_*_packed_dev)
+hipError_t launch_replace_groups_lengths(const ReplaceGroupsArgs &a, int n_cus, hipStream_t stream);
+hipError_t launch_replace_groups_fill(const ReplaceGroupsArgs &a, int n_cus, hipStream_t stream);
 // needle_gather.hip: spans of packed rows as a new packed batch (needle_gather_spans_*_packed_dev), a match list's complement
 // (needle_split_spans_packed_dev); the spans the fill kernel tables at once
 hipError_t launch_gather_lengths(const GatherArgs &a, int n_cus, hipStream_t stream);

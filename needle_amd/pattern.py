@@ -1721,6 +1721,159 @@ class Pattern:
         text, off = text.cpu().numpy(), off.cpu().numpy()
         return [text[off[i]:off[i + 1]].tobytes() for i in range(len(rows))]
 
+    # ---- replace matches by a template with group references: "$2-$1" (needle_template_parse, needle_replace_groups_*_packed_dev)
+    def parse_template(self, repl):
+        """A replacement template (a str, read as UTF-16 code units) by the rules of java.util.regex's Matcher.appendReplacement for this
+        pattern's group_count() -> (groups, literals): K group numbers and K + 1 literal strs, the template being
+        literals[0] + $groups[0] + literals[1] + ... + literals[K].  `\\x` is x, `$12` takes digits while the number names a group, `${name}`
+        is refused.  Needs no device; ValueError carries the library's message (position and rule)."""
+        L = _lib.lib()
+        u = np.ascontiguousarray(_utf16(repl))
+        groups = np.zeros(_lib.TEMPLATE_MAX_REFS, dtype=np.int32)
+        loff = np.zeros(_lib.TEMPLATE_MAX_REFS + 2, dtype=np.uint32)
+        lits = np.zeros(max(u.size, 1), dtype=np.uint16)  # (the literals are never longer than the template)
+        k, nl = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = L.needle_template_parse(u.ctypes.data if u.size else None, u.size, self.group_count(), groups.ctypes.data, groups.size, loff.ctypes.data,
+                                     loff.size, lits.ctypes.data, lits.size, ctypes.byref(k), ctypes.byref(nl))
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(_lib.last_error())
+        _check(rc)
+        text = lambda a: a.tobytes().decode("utf-16-le", "surrogatepass")
+        return groups[:k.value].tolist(), [text(lits[loff[i]:loff[i + 1]]) for i in range(k.value + 1)]
+
+    @staticmethod
+    def _template(groups, literals, char_width, n_planes):
+        """(groups, literals) as a needle_template of the rows' char width -> (the structure, the arrays it points into).  ValueError: not
+        K + 1 literals, more than 16 references, a group that is no plane, a unit the rows cannot hold, more than 4096 units in all."""
+        groups, literals = [int(g) for g in groups], list(literals)
+        if len(literals) != len(groups) + 1:
+            raise ValueError("a template of K references has K + 1 literals (got %d and %d)" % (len(groups), len(literals)))
+        if len(groups) > _lib.TEMPLATE_MAX_REFS:
+            raise ValueError("a template holds at most %d group references" % _lib.TEMPLATE_MAX_REFS)
+        for g in groups:
+            if not 0 <= g < n_planes:
+                raise ValueError("group %d is outside the %d planes" % (g, n_planes))
+        parts = [Pattern._repl_units(x, char_width) for x in literals]
+        loff = np.zeros(len(parts) + 1, dtype=np.uint32)
+        loff[1:] = np.cumsum([p.size for p in parts])
+        if int(loff[-1]) > _lib.REPLACE_MAX_UNITS:
+            raise ValueError("template literals longer than %d code units" % _lib.REPLACE_MAX_UNITS)
+        g, units = np.asarray(groups, dtype=np.int32), np.ascontiguousarray(np.concatenate(parts))
+        t = _lib.Template()
+        t.n_refs, t.groups, t.lit_offsets, t.lits = len(groups), g.ctypes.data if g.size else None, loff.ctypes.data, units.ctypes.data if units.size else None
+        return t, (g, loff, units)
+
+    @staticmethod
+    def splice_groups_packed(data, offsets, match_offsets, gstart, gend, groups, literals, stream=None, out=None, out_start=0):
+        """splice_packed with a TEMPLATE per match (needle_replace_groups_lengths_packed_dev, torch cumsum,
+        needle_replace_groups_fill_packed_dev on one stream): match m of the caller's CSR list -- column m of the int32 planes gstart / gend
+        [n_planes, stride], what captures_spans_packed returns, plane 0 the match itself -- is replaced by
+        literals[0] + group groups[0] + literals[1] + ... + literals[K], or KEPT where gstart[0, m] < 0; a group with gstart[g, m] < 0
+        contributes nothing -> (out_data, out_offsets int64[n + 1]).  groups / literals: what parse_template returns (literals: str or 1-D
+        arrays of code units).  Pure: no pattern.  out / out_start (device inputs only) and the one host read: as splice_packed; numpy
+        inputs are uploaded, spliced on the device and brought back, and take neither out nor out_start."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            assert out is None and out_start == 0, "out / out_start go with device inputs"
+            d, (o, mo) = Pattern._gather_host_args(data, ((offsets, np.int64), (match_offsets, np.int64)))
+            pl = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to("cuda")
+            text, off = Pattern.splice_groups_packed(d, o, mo, pl(gstart), pl(gend), groups, literals, stream)
+            return Pattern._gather_host_text(text), off.cpu().numpy()
+        Pattern._gather_check(data, ((offsets, torch.int64, "offsets"), (match_offsets, torch.int64, "match_offsets")))
+        for t, what in ((gstart, "gstart"), (gend, "gend")):
+            assert isinstance(t, torch.Tensor) and t.device == data.device and t.dtype == torch.int32 and t.dim() == 2 and t.is_contiguous(), what
+        assert gstart.shape == gend.shape, "gstart / gend: two planes arrays of one shape"
+        n, dv, cw = offsets.numel() - 1, data.device, data.element_size()
+        assert n >= 0 and match_offsets.numel() == n + 1
+        planes, stride = gstart.size(0), gstart.size(1)
+        tm, keep = Pattern._template(groups, literals, cw, planes)
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), cw, n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            s = one.cuda_stream
+            sp, ep = (gstart.data_ptr(), gend.data_ptr()) if gstart.numel() else (None, None)
+            lens = torch.empty(n, dtype=torch.int64, device=dv)
+            _check(L.needle_replace_groups_lengths_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, stride, planes, ctypes.byref(tm),
+                                                              lens.data_ptr(), s))
+            out_off = torch.full((n + 1,), int(out_start), dtype=torch.int64, device=dv)
+            if n:
+                out_off[1:] += torch.cumsum(lens, 0)
+            total = int(out_off[-1].item())
+            if out is None:
+                room = torch.empty(total + 4, dtype=data.dtype, device=dv)  # (never an empty allocation: its pointer would be NULL)
+                out = room[:total]
+            else:
+                assert out.device == dv and out.dtype == data.dtype and out.dim() == 1 and out.is_contiguous() and out.numel() >= total
+                room = out
+            _check(L.needle_replace_groups_fill_packed_dev(ctypes.byref(v), match_offsets.data_ptr(), sp, ep, stride, planes, ctypes.byref(tm),
+                                                           out_off.data_ptr(), room.data_ptr(), s))
+        del keep
+        return out, out_off
+
+    def _need_captures(self, char_width):
+        info = self.captures_info(char_width)
+        if not info["available"]:
+            raise PatternException("group references need this pattern's capturing groups, which are refused: %s" % info["reason"])
+
+    def replace_all_groups_packed(self, data, offsets, repl, stream=None, out=None, out_start=0):
+        """Every match of every packed row -- find_all_packed's list -- replaced by the template `repl` with its group references filled
+        in ("$2-$1"; parse_template's syntax) -> (out_data, out_offsets): find_all_groups_packed, then splice_groups_packed, on one
+        stream.  java.util.regex's replaceAll(String) wherever the list is its find() loop's (see replace_all_packed).  A pattern whose
+        captures are refused raises PatternException with the reason.  numpy inputs are uploaded and the result brought back."""
+        groups, literals = self.parse_template(repl)
+        host = isinstance(data, np.ndarray)
+        self._need_captures(data.itemsize if host else data.element_size())
+        if host:
+            data, (offsets,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+        off, gs, ge = self.find_all_groups_packed(data, offsets, stream)
+        text, toff = Pattern.splice_groups_packed(data, offsets, off, gs, ge, groups, literals, stream=stream, out=out, out_start=out_start)
+        return (Pattern._gather_host_text(text), toff.cpu().numpy()) if host else (text, toff)
+
+    def replace_first_groups_packed(self, data, offsets, repl, stream=None, out=None, out_start=0):
+        """The first match of every packed row (find_packed's) replaced by the template `repl`: find_packed's results as a list of at most
+        one match per row (as replace_first_packed builds it), captures_spans_packed on that list, then splice_groups_packed."""
+        import torch
+        groups, literals = self.parse_template(repl)
+        host = isinstance(data, np.ndarray)
+        self._need_captures(data.itemsize if host else data.element_size())
+        if host:
+            data, (offsets,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+        dv, n = data.device, offsets.numel() - 1
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            words, st, en = self.find_packed(data, offsets, stream=stream)
+            hit = ((words.unsqueeze(1) >> torch.arange(64, device=dv)) & 1).reshape(-1)[:n].bool()
+            moff = torch.zeros(n + 1, dtype=torch.int64, device=dv)
+            if n:
+                torch.cumsum(hit, 0, out=moff[1:])
+            st1, en1 = st[:n][hit].contiguous(), en[:n][hit].contiguous()
+        gs, ge = self.captures_spans_packed(data, offsets, moff, st1, en1, stream)
+        text, toff = Pattern.splice_groups_packed(data, offsets, moff, gs, ge, groups, literals, stream=stream, out=out, out_start=out_start)
+        return (Pattern._gather_host_text(text), toff.cpu().numpy()) if host else (text, toff)
+
+    def replace_all_groups_strings(self, strings, repl):
+        """Every match of every str replaced by the template `repl` -> list[str] (UTF-16 code units, like java.lang.String):
+        pack_strings + replace_all_groups_packed.  compile(r"([0-9]+)-([0-9]+)").replace_all_groups_strings(["10-20"], "$2-$1") == ["20-10"]."""
+        data, offsets = pack_strings(strings)
+        text, off = self.replace_all_groups_packed(data, offsets, repl)
+        return [text[off[i]:off[i + 1]].tobytes().decode("utf-16-le", "surrogatepass") for i in range(len(strings))]
+
+    def replace_all_groups_bytes(self, rows, repl):
+        """replace_all_groups_strings for UTF-8 `bytes` rows -> list[bytes]: find_all_groups_utf8_packed for the groups' BYTE positions, then
+        splice_groups_packed at char width 1 on the ORIGINAL bytes with each literal of the template (a str) encoded to UTF-8.  No encoder
+        runs over the text: the bytes of ill-formed input outside the matches come back untouched."""
+        groups, literals = self.parse_template(repl.decode("utf-8") if isinstance(repl, (bytes, bytearray)) else repl)
+        self._need_captures(2)
+        lits = [np.frombuffer(x.encode("utf-8"), dtype=np.uint8) for x in literals]
+        data, offsets = pack_bytes(rows)
+        d, o, _ = Pattern._utf8_dev(data, offsets)
+        moff, bs, be = self.find_all_groups_utf8_packed(d, o)
+        text, off = Pattern.splice_groups_packed(d, o, moff, bs, be, groups, lits)
+        text, off = text.cpu().numpy(), off.cpu().numpy()
+        return [text[off[i]:off[i + 1]].tobytes() for i in range(len(rows))]
+
     # ---- a file as a packed batch: lines_packed in front of the UTF-8 chain (needle_lines_*_packed_dev)
     def _grep_lines(self, buf):
         """A UTF-8 file -> (its lines without terminators as a packed device batch, the bitmap words of the lines that contain a match):
