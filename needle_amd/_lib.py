@@ -12,6 +12,7 @@ REPLACE_MAX_CHOICES = 256  # NEEDLE_REPLACE_MAX_CHOICES
 TEMPLATE_MAX_REFS = 16  # NEEDLE_TEMPLATE_MAX_REFS
 CHOICE_INDEX, CHOICE_LOWEST_BIT = 0, 1  # NEEDLE_CHOICE_INDEX, NEEDLE_CHOICE_LOWEST_BIT
 GATHER_MATCHES, GATHER_PIECES = 0, 1  # NEEDLE_GATHER_MATCHES, NEEDLE_GATHER_PIECES
+GROUP_NONE = 0xFFFFFFFFFFFFFFFF  # NEEDLE_GROUP_NONE
 UTF8_MAX_EXPANSION = 1  # NEEDLE_UTF8_MAX_EXPANSION: units(row) <= bytes(row)
 LINES_KEEP_ENDS = 1  # NEEDLE_LINES_KEEP_ENDS
 CAPTURES_MAX_GROUPS = 16  # NEEDLE_CAPTURES_MAX_GROUPS
@@ -32,7 +33,7 @@ EXPORTS = [
     "needle_replace_each_lengths_packed_dev", "needle_replace_each_fill_packed_dev", "needle_set_replace_each_packed_host",
     "needle_template_parse", "needle_replace_groups_lengths_packed_dev", "needle_replace_groups_fill_packed_dev",
     "needle_gather_spans_lengths_packed_dev", "needle_gather_spans_fill_packed_dev", "needle_split_spans_packed_dev", "needle_gather_chunk_spans",
-    "needle_gather_matches_packed_host",
+    "needle_gather_matches_packed_host", "needle_group_spans_work_bytes", "needle_group_spans_packed_dev",
     "needle_utf16_lengths_from_utf8_packed_dev", "needle_utf16_from_utf8_packed_dev", "needle_utf8_positions_packed_dev", "needle_utf8_window_bytes",
     "needle_contained_in_utf8_packed_host", "needle_find_all_csr_utf8_packed_host",
     "needle_lines_tile_units", "needle_lines_tiles", "needle_lines_count_packed_dev", "needle_lines_fill_packed_dev",
@@ -205,6 +206,9 @@ def lib():
     L.needle_gather_chunk_spans.argtypes = []
     L.needle_gather_chunk_spans.restype = ctypes.c_uint32
     L.needle_gather_matches_packed_host.argtypes = [VP, P(PackedView), I, VP, VP, ctypes.c_uint64, VP, ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64)]
+    L.needle_group_spans_work_bytes.argtypes = [ctypes.c_uint64]
+    L.needle_group_spans_work_bytes.restype = ctypes.c_uint64
+    L.needle_group_spans_packed_dev.argtypes = [P(PackedView), VP, VP, VP, ctypes.c_uint64, U32, VP, ctypes.c_uint64, VP, VP, VP, VP]
     L.needle_utf16_lengths_from_utf8_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP]
     L.needle_utf16_from_utf8_packed_dev.argtypes = [P(PackedView), VP, VP, VP]
     L.needle_utf8_positions_packed_dev.argtypes = [P(PackedView), VP, VP, VP, VP]

@@ -10,7 +10,7 @@ SOURCES = ["needle_scan_find1.hip", "needle_scan_find2.hip", "needle_scan_contai
            "needle_packed_find2.hip", "needle_packed_contained.hip", "needle_packed_matches.hip", "needle_packed_next1.hip", "needle_packed_next2.hip", "needle_packed_forms1.hip", "needle_packed_forms2.hip", "needle_packed_find_all1.hip",
            "needle_packed_find_all2.hip", "needle_packed_find_all_lane1.hip", "needle_packed_find_all_lane2.hip", "needle_packed_set1.hip", "needle_packed_set2.hip", "needle_set_spans1.hip", "needle_set_spans2.hip", "needle_captures_spans1.hip", "needle_captures_spans2.hip", "needle_kernels.hip",
            "needle_stripe.hip", "needle_find_all.hip", "needle_find_all_ls.hip", "needle_compact.hip", "needle_ngram.hip", "needle_ngram_packed_contained1.hip", "needle_ngram_packed_contained2.hip", "needle_ngram_packed_find1.hip",
-           "needle_ngram_packed_find2.hip", "needle_ngram_packed_find_all1.hip", "needle_ngram_packed_find_all2.hip", "needle_replace.hip", "needle_replace_each.hip", "needle_replace_groups.hip", "needle_gather.hip", "needle_utf8.hip", "needle_lines.hip", "needle_ngram_host.cpp", "needle_api.cpp", "needle_host.cpp", "needle_tuning.cpp", "needle_multi.cpp", "needle_lower.cpp", "needle_set.cpp", "needle_regex.cpp", "needle_captures.cpp"]
+           "needle_ngram_packed_find2.hip", "needle_ngram_packed_find_all1.hip", "needle_ngram_packed_find_all2.hip", "needle_replace.hip", "needle_replace_each.hip", "needle_replace_groups.hip", "needle_gather.hip", "needle_group.hip", "needle_utf8.hip", "needle_lines.hip", "needle_ngram_host.cpp", "needle_api.cpp", "needle_host.cpp", "needle_tuning.cpp", "needle_multi.cpp", "needle_lower.cpp", "needle_set.cpp", "needle_regex.cpp", "needle_captures.cpp"]
 
 
 TUNING_LIB = os.path.join(HERE, "libneedle_hip_tuning.so")

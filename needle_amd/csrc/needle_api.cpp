@@ -1843,6 +1843,61 @@ int needle_split_spans_packed_dev(const needle_packed_view *v, const uint64_t *d
 
 uint32_t needle_gather_chunk_spans(void) { return gather_chunk_spans(); }
 
+// Equal spans of a list put into groups (needle_group.hip): a pure function of (text, span list) in the caller's workspace.  Every check
+// runs before any device call; the table and the status are cleared on the stream, then the three kernels follow in stream order.
+uint64_t needle_group_spans_work_bytes(uint64_t max_spans) { return group_layout(std::min<uint64_t>(max_spans, kGroupMaxSpans)).total; }
+
+int needle_group_spans_packed_dev(const needle_packed_view *v, const uint64_t *d_span_offsets, const int32_t *d_start, const int32_t *d_end,
+                                  uint64_t max_spans, uint32_t hash_bits, void *d_work, uint64_t work_bytes, uint64_t *d_first,
+                                  uint32_t *d_count, uint32_t *d_status, void *stream_) {
+    int rc = check_packed(v), cus = 0;
+    if (rc) return rc;
+    if (((uintptr_t)v->data) % 4 != 0) return fail(NEEDLE_ERR_INVALID, "packed data must be 4-byte aligned");
+    if (!d_span_offsets) return fail(NEEDLE_ERR_INVALID, "span offsets is NULL");
+    if ((d_start == nullptr) != (d_end == nullptr)) return fail(NEEDLE_ERR_INVALID, "start / end: one of them is NULL");
+    if (!d_start && max_spans != 0) return fail(NEEDLE_ERR_INVALID, "start / end may be NULL only with max_spans == 0");
+    if (max_spans > kGroupMaxSpans) return fail(NEEDLE_ERR_INVALID, "max_spans is above 2^32 - 2");
+    if (hash_bits > 64) return fail(NEEDLE_ERR_INVALID, "hash_bits is above 64");
+    if (!d_first || !d_count) return fail(NEEDLE_ERR_INVALID, "output buffer is NULL");
+    if (!d_status) return fail(NEEDLE_ERR_INVALID, "status is NULL");
+    if (!d_work) return fail(NEEDLE_ERR_INVALID, "workspace is NULL");
+    if (((uintptr_t)d_work) % 16 != 0) return fail(NEEDLE_ERR_INVALID, "workspace must be 16-byte aligned");
+    const GroupLayout lay = group_layout(max_spans);
+    if (work_bytes < lay.total) return fail(NEEDLE_ERR_INVALID, "workspace is smaller than needle_group_spans_work_bytes(max_spans)");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (v->n_rows == 0) {
+        HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream));
+        return NEEDLE_OK;
+    }
+    if ((rc = gather_cus(&cus))) return rc;
+    uint8_t *w = (uint8_t *)d_work;
+    GroupArgs a;
+    memset(&a, 0, sizeof(a));
+    a.data = (const uint8_t *)v->data;
+    a.in_off = v->offsets;
+    a.n_rows = v->n_rows;
+    a.cw = v->char_width;
+    a.span_off = d_span_offsets;
+    a.start = d_start;
+    a.end = d_end;
+    a.max_spans = max_spans;
+    a.hash_mask = group_hash_mask(hash_bits);
+    a.slots = lay.slots;
+    a.w_addr = (uint64_t *)(w + lay.addr);
+    a.w_hash = (uint64_t *)(w + lay.hash);
+    a.w_slot = (uint64_t *)(w + lay.slot);
+    a.w_len = (uint32_t *)(w + lay.len);
+    a.w_word = (uint32_t *)(w + lay.word);
+    a.w_count = (uint32_t *)(w + lay.count);
+    a.first = d_first;
+    a.count = d_count;
+    a.status = d_status;
+    HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(w + lay.clear_at, 0, lay.clear_bytes, stream));
+    HIP_TRY(launch_group_spans(a, cus, stream));
+    return NEEDLE_OK;
+}
+
 // The UTF-8 front door (needle_utf8.hip): pure functions of the text (and a position list) -- no pattern, no route.  The checks all
 // three entries share, then the kernels' arguments and the device's CU count (n_rows == 0: not reached).
 static int utf8_view_check(const needle_packed_view *v) {

@@ -9,6 +9,7 @@
 #include "needle_device.h"
 #include "needle_find_all.h"
 #include "needle_gather.h"
+#include "needle_group.h"
 #include "needle_lines.h"
 #include "needle_ngram.h"
 #include "needle_replace.h"
@@ -94,6 +95,8 @@ hipError_t launch_gather_lengths(const GatherArgs &a, int n_cus, hipStream_t str
 hipError_t launch_gather_fill(const GatherArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_split_spans(const GatherArgs &a, int n_cus, hipStream_t stream);
 uint32_t gather_chunk_spans();
+// needle_group.hip: equal spans of a CSR list put into groups (needle_group_spans_packed_dev): hash, insert, finish on one stream
+hipError_t launch_group_spans(const GroupArgs &a, int n_cus, hipStream_t stream);
 // needle_utf8.hip: UTF-8 packed rows -> UTF-16 packed rows (lengths, fill), unit positions -> byte offsets; the text a wave takes per step
 hipError_t launch_utf8_lengths(const Utf8Args &a, int n_cus, hipStream_t stream);
 hipError_t launch_utf8_fill(const Utf8Args &a, int n_cus, hipStream_t stream);

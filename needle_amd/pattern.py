@@ -1297,6 +1297,134 @@ class Pattern:
                                                    room.data_ptr() + 4 * pieces, one.cuda_stream))
         return po, room[:pieces], room[pieces:2 * pieces]
 
+    # ---- distinct spans and their counts: equal spans of a list put into groups (needle_group_spans_packed_dev)
+    @staticmethod
+    def group_spans_packed(data, offsets, span_offsets, start, end, stream=None, hash_bits=64):
+        """needle_group_spans_packed_dev: per span of a CSR list over packed rows the FIRST span with the same (clamped) text and the size
+        of its group -> (first int64[M], count int32[M]) on the device, indexed like `start`: first[m] is the smallest index whose text
+        equals span m's, count[m] the number of such spans.  A span with start < 0 and end < 0 is absent (an unpassed capture group):
+        first -1 (NEEDLE_GROUP_NONE), count 0 -- as have the entries outside [span_offsets[0], span_offsets[n]).  The leaders, first[m]
+        == m, are the distinct texts in first-occurrence order.  Exact (texts are compared, not hashes) and deterministic.  The
+        workspace is sized from start.numel(); the one host read is the status, and status 1 (more spans named by span_offsets than start /
+        end hold, or a full table) raises, also for an empty start / end.  hash_bits (0 .. 64) never changes
+        the result: fewer bits make different texts share probe chains (tests).  numpy inputs are uploaded and the results brought back."""
+        import torch
+        L = _lib.lib()
+        if isinstance(data, np.ndarray):
+            d, (o, so, st, en) = Pattern._gather_host_args(data, ((offsets, np.int64), (span_offsets, np.int64), (start, np.int32), (end, np.int32)))
+            return tuple(x.cpu().numpy() for x in Pattern.group_spans_packed(d, o, so, st, en, stream, hash_bits))
+        Pattern._gather_check(data, ((offsets, torch.int64, "offsets"), (span_offsets, torch.int64, "span_offsets"), (start, torch.int32, "start"),
+                                     (end, torch.int32, "end")))
+        n, dv, m = offsets.numel() - 1, data.device, start.numel()
+        assert n >= 0 and span_offsets.numel() == n + 1 and end.numel() == m, "span_offsets: n_rows + 1 entries; start / end alike"
+        v = _lib.PackedView()
+        v.data, v.char_width, v.n_rows, v.offsets = data.data_ptr(), data.element_size(), n, offsets.data_ptr()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            first_room = torch.full((m + 1,), -1, dtype=torch.int64, device=dv)  # (never an empty tensor: its pointer would be NULL)
+            count_room = torch.zeros(m + 1, dtype=torch.int32, device=dv)
+            first, count = first_room[:m], count_room[:m]
+            if n == 0:
+                return first, count
+            work_bytes = int(L.needle_group_spans_work_bytes(m))
+            work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=dv)
+            status = torch.zeros(1, dtype=torch.int32, device=dv)
+            sp, ep = (start.data_ptr(), end.data_ptr()) if m else (None, None)  # (no spans: the status still says whether the offsets agree)
+            _check(L.needle_group_spans_packed_dev(ctypes.byref(v), span_offsets.data_ptr(), sp, ep, m, hash_bits,
+                                                   work.data_ptr(), work_bytes, first_room.data_ptr(), count_room.data_ptr(), status.data_ptr(),
+                                                   one.cuda_stream))
+            if int(status.item()) != 0:
+                raise DeviceError("needle_group_spans_packed_dev: status 1 -- the span offsets name more spans than start / end hold "
+                                  "(max_spans), or the table filled")
+        return first, count
+
+    @staticmethod
+    def distinct_spans_packed(data, offsets, span_offsets, start, end, stream=None):
+        """The distinct texts of a span list and how often each occurs (grep -o | sort | uniq -c without the sort) -> (text, text_offsets,
+        counts int32[k], group_of_span int64[M]): distinct text g -- in first-occurrence order -- is text[text_offsets[g]:text_offsets[g +
+        1]] and occurs counts[g] times; span m belongs to group_of_span[m] (-1: an absent span, or an entry outside the list).
+        group_spans_packed, the leaders by first == arange, group ids by a cumsum over the leaders, the leaders' own CSR list over the
+        rows, gather_spans_packed on it: everything stays on the device, and (text, text_offsets) is a packed batch every entry takes.
+        numpy inputs are uploaded and the results brought back."""
+        import torch
+        if isinstance(data, np.ndarray):
+            d, (o, so, st, en) = Pattern._gather_host_args(data, ((offsets, np.int64), (span_offsets, np.int64), (start, np.int32), (end, np.int32)))
+            text, toff, counts, gid = Pattern.distinct_spans_packed(d, o, so, st, en, stream)
+            return Pattern._gather_host_text(text), toff.cpu().numpy(), counts.cpu().numpy(), gid.cpu().numpy()
+        first, count = Pattern.group_spans_packed(data, offsets, span_offsets, start, end, stream)
+        dv, m = data.device, start.numel()
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            leader = first == torch.arange(m, dtype=torch.int64, device=dv)
+            before = torch.zeros(m + 1, dtype=torch.int64, device=dv)  # leaders in front of entry m
+            if m:
+                torch.cumsum(leader, 0, out=before[1:])
+            gid = torch.where(first >= 0, before[first.clamp(min=0)], torch.full_like(first, -1))
+            lso = before[span_offsets.clamp(0, m)]  # the leaders' list over the rows (no leader lies in front of span_offsets[0])
+            lst, len_, counts = start[leader].contiguous(), end[leader].contiguous(), count[leader].contiguous()
+        text, toff = Pattern.gather_spans_packed(data, offsets, lso, lst, len_, stream=stream)
+        return text, toff, counts, gid
+
+    def distinct_matches_packed(self, data, offsets, stream=None):
+        """The distinct matches of every packed row and their counts -> (text, text_offsets, counts, group_of_match) as
+        distinct_spans_packed, on find_all_packed's list.  numpy inputs are uploaded and the results brought back."""
+        if isinstance(data, np.ndarray):
+            d, (o,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+            text, toff, counts, gid = self.distinct_matches_packed(d, o, stream)
+            return Pattern._gather_host_text(text), toff.cpu().numpy(), counts.cpu().numpy(), gid.cpu().numpy()
+        off, st, en = self.find_all_packed(data, offsets, stream=stream)
+        return Pattern.distinct_spans_packed(data, offsets, off, st, en, stream=stream)
+
+    @staticmethod
+    def _distinct_table(text, toff, counts, decode):
+        text, toff, counts = np.asarray(text), np.asarray(toff), np.asarray(counts)
+        return [(decode(text[toff[g]:toff[g + 1]]), int(counts[g])) for g in range(counts.size)]
+
+    def count_distinct_strings(self, strings):
+        """The distinct matches over all strs and how often each occurs -> list[(str, int)] in first-occurrence order
+        (collections.Counter over re.findall, insertion-ordered): pack_strings + distinct_matches_packed."""
+        data, offsets = pack_strings(strings)
+        text, toff, counts, _ = self.distinct_matches_packed(data, offsets)
+        return Pattern._distinct_table(text, toff, counts, lambda u: u.tobytes().decode("utf-16-le", "surrogatepass"))
+
+    def count_distinct_bytes(self, rows):
+        """count_distinct_strings for UTF-8 `bytes` rows -> list[(bytes, int)]: find_all_utf8_packed's byte positions, grouped at char
+        width 1 on the ORIGINAL bytes -- no encoder back to UTF-8 is involved; matches are equal when their bytes are."""
+        data, offsets = pack_bytes(rows)
+        d, o, _ = Pattern._utf8_dev(data, offsets)
+        moff, bs, be = self.find_all_utf8_packed(d, o)
+        text, toff, counts, _ = Pattern.distinct_spans_packed(d, o, moff, bs, be)
+        return Pattern._distinct_table(text.cpu().numpy(), toff.cpu().numpy(), counts.cpu().numpy(), lambda u: u.tobytes())
+
+    def count_distinct_group_strings(self, strings, g):
+        """The distinct texts of capturing group g over every match of every str -> list[(str, int)] in first-occurrence order (GROUP BY
+        regexp_extract(.., g)): plane g of find_all_groups_packed through distinct_spans_packed.  A group the match did not pass is
+        absent: it is not reported and counts for nobody."""
+        data, offsets = pack_strings(strings)
+        d, (o,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+        off, gs, ge = self.find_all_groups_packed(d, o)
+        assert 0 <= g < gs.size(0), "group out of range"
+        text, toff, counts, _ = Pattern.distinct_spans_packed(d, o, off, gs[g].contiguous(), ge[g].contiguous())
+        return Pattern._distinct_table(Pattern._gather_host_text(text), toff.cpu().numpy(), counts.cpu().numpy(),
+                                       lambda u: u.tobytes().decode("utf-16-le", "surrogatepass"))
+
+    @staticmethod
+    def distinct_rows_packed(data, offsets, stream=None):
+        """The distinct rows of a packed batch and their counts (sort -u / uniq -c of lines without the sort) -> (text, text_offsets,
+        counts, group_of_row) as distinct_spans_packed, with the list (0, 2^31 - 1) for every row: the clamp makes the span the row."""
+        import torch
+        if isinstance(data, np.ndarray):
+            d, (o,) = Pattern._gather_host_args(data, ((offsets, np.int64),))
+            text, toff, counts, gid = Pattern.distinct_rows_packed(d, o, stream)
+            return Pattern._gather_host_text(text), toff.cpu().numpy(), counts.cpu().numpy(), gid.cpu().numpy()
+        n, dv = offsets.numel() - 1, data.device
+        one = torch.cuda.current_stream(dv) if stream is None else torch.cuda.ExternalStream(stream, device=dv)
+        with torch.cuda.device(dv), torch.cuda.stream(one):
+            so = torch.arange(n + 1, dtype=torch.int64, device=dv)
+            st = torch.zeros(n, dtype=torch.int32, device=dv)
+            en = torch.full((n,), 0x7FFFFFFF, dtype=torch.int32, device=dv)
+        return Pattern.distinct_spans_packed(data, offsets, so, st, en, stream=stream)
+
     def _gather_matches_host(self, mode, data, offsets):
         """needle_gather_matches_packed_host on numpy data + offsets: first with guessed capacities, then with the exact totals."""
         L = _lib.lib()

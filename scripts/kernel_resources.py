@@ -4,6 +4,7 @@ rows, of the packed-rows scan kernel, of the packed-rows find-all kernels (trans
 of the pattern-set kernel of span lists (needle_set_spans.h), of the capture kernel of span lists (needle_captures_spans.h) and of the n-gram filter kernels (fixed-stride rows: needle_ngram.hip; packed rows: needle_ngram_packed_*.hip) and of the replace kernels
 (needle_replace.hip, needle_replace_each.hip, needle_replace_groups.hip: 4 waves per workgroup, static LDS) and of the gather kernels (needle_gather.hip: the same) and of the UTF-8 kernels (needle_utf8.hip: the same)
 and of the line-splitting kernels (needle_lines.hip: one workgroup of 256 lanes per tile, static LDS)
+and of the grouping kernels (needle_group.hip: 4 waves per workgroup; the hash kernel's offsets in static LDS)
 (cross-compiled here, no
 GPU needed): the kernels run 16 waves per workgroup, i.e. at most 128 VGPRs; anything above spills.  The packed-rows kernels'
 LDS is the program plus one window (the tile) per wave, sized at launch: listed as the window per wave.
@@ -22,7 +23,7 @@ for tu in ("needle_scan_matches", "needle_scan_contained", "needle_scan_find1", 
            "needle_packed_find_all1", "needle_packed_find_all2", "needle_packed_find_all_lane1", "needle_packed_find_all_lane2",
            "needle_packed_set1", "needle_packed_set2", "needle_set_spans1", "needle_set_spans2", "needle_captures_spans1", "needle_captures_spans2",
            "needle_ngram", "needle_ngram_packed_contained1", "needle_ngram_packed_contained2", "needle_ngram_packed_find1", "needle_ngram_packed_find2",
-           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace", "needle_replace_each", "needle_replace_groups", "needle_gather", "needle_utf8", "needle_lines"):
+           "needle_ngram_packed_find_all1", "needle_ngram_packed_find_all2", "needle_replace", "needle_replace_each", "needle_replace_groups", "needle_gather", "needle_group", "needle_utf8", "needle_lines"):
     out = os.path.join(tmp, tu + ".s")
     procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
                                          "-S", "-o", out, os.path.join(CSRC, tu + ".hip")], stderr=subprocess.DEVNULL)))
@@ -130,6 +131,12 @@ for k, sc, v in sorted(rows):
     m = re.search(r"(gather_lengths|split_spans|gather_fill)_kernel(?:ILi(\d)E)?", k)
     if m:
         print("%4d %4d %6d  %-14s %s" % (sc, v, lds.get(k, 0), m.group(1).replace("_", " "), "cw" + m.group(2) if m.group(2) else ""))
+# the grouping kernels (needle_group.hip): the hash per char width, insert, finish
+print("grouping kernels (needle_group.hip): scratch bytes / VGPRs / LDS bytes per workgroup / kernel")
+for k, sc, v in sorted(rows):
+    m = re.search(r"group_(hash|insert|finish)_kernel(?:ILi(\d)E)?", k)
+    if m:
+        print("%4d %4d %6d  group %-6s %s" % (sc, v, lds.get(k, 0), m.group(1), "cw" + m.group(2) if m.group(2) else ""))
 # the UTF-8 kernels (needle_utf8.hip): lengths and fill (position-parallel), positions (lane = row)
 print("UTF-8 kernels (needle_utf8.hip): scratch bytes / VGPRs / LDS bytes per workgroup / kernel")
 for k, sc, v in sorted(rows):
